@@ -2,11 +2,25 @@
 
     python bench.py --gpus N --steps K --warmup W        (N>1: spawns N ranks itself via torch.distributed.run, or runs as a rank when
                                                           the launcher's RANK / WORLD_SIZE are already in the environment)
+    python bench.py ... --full                           (adds the roofline leg, the CPU baseline and, for N=1, the fp32-gradient and
+                                                          data-parallel legs in child processes)
+    python bench.py ... --dump-outputs DIR               (after the timed steps: what one more step computes, DIR/<name>.npy)
+
+--dump-outputs writes the step's loss and network outputs (logits; loc / conf for the detector): two runs reproduce the logits bit for bit
+and the loss, an atomic mean, to a few ulps.  Two things keep the rest out.  (1) The backward sums with fp32 atomics, and fake-quant index
+flips amplify those last-bit differences from step to step: after 3 eager + 25 replayed steps at B = 512 two runs of one build hold
+models 3e-2 apart and O(1) different logits.  So for the training workloads the written step starts from the seeded state every run
+starts from: parameters, buffers, observer ranges, optimizer state and dropout stream are put back to what they were before the first
+step, and the timed step (the captured graph) runs once more.  (2) Even that one step's gradients differ between two runs by 2e-2
+(relative norm; up to 4e-4 absolute in the updated parameters at B = 512): the atomics' order again, through BatchNorm's cancelling sums and
+bf16 gradient storage.  Gradients and updated parameters are therefore not written.  The float warm-up workload (--workload float) in
+its default bf16 storage is the exception: its forward itself spreads between runs (2e-2 relative in the logits; atomics order x bf16
+storage), and its dumps reproduce bit for bit only in fp32 storage (FROST_FLOAT_PRECISION=fp32).
 
 One "step" = one pass of the hot path over one synthetic batch: fake-quantised forward (int8 MFMA / LDS depthwise),
 hand-written backward, GradBoost-SGD multi-tensor update; for N>1 plus the bucketed RCCL gradient all-reduce
 overlapped with backward.  Per-GPU batch is fixed (weak scaling).  Inputs are resident in HBM before the timed region.
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Rank 0 prints ONE JSON line; `roofline` and `cpu_baseline` are filled in by --full, null otherwise.
 """
 import argparse
 import json
@@ -18,6 +32,49 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+DUMP_BUDGET = 60 << 20        # --dump-outputs writes at most this many bytes of array data (64 MB in all with the .npy headers)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every tensor of `arrays` as <dirname>/<name>.npy, float32 (float64 stays float64).  If together they exceed DUMP_BUDGET,
+    each keeps the same share of its elements, a fixed seeded sample of the flattened tensor, so runs of the same arguments compare element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.detach().to(torch.float64 if v.dtype == torch.float64 else torch.float32) for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_BUDGET:
+            keep = v.numel() * DUMP_BUDGET // total
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(1882))[:keep].sort().values
+            v = v.reshape(-1)[idx.to(v.device)]
+        np.save(os.path.join(dirname, name + ".npy"), v.cpu().numpy())
+    print(f"[bench] wrote {', '.join(sorted(arrays))} to {dirname}", file=sys.stderr, flush=True)
+
+
+def initial_state(model, runner):
+    """Copies of the seeded state a training run starts from, taken before its first step: parameters, buffers and the runner's qrecord arena
+    (BatchNorm statistics, observer ranges, qparams), and the position of the dropout stream."""
+    ts = [p.data for p in model.parameters()] + list(model.buffers())
+    qa = getattr(getattr(runner, "qa", None), "t", None)
+    if qa is not None:
+        ts.append(qa)
+    return dict(tensors=[(t, t.detach().clone()) for t in ts], rng=runner.rng_state())
+
+
+def restore_state(init, opt, runner):
+    """Put the training state back to `initial_state`'s copies, IN PLACE (a captured hipGraph holds these addresses).  The optimizer's state is
+    created at its first step as zero tensors with step counters at 0 (GradBoost _init_state): it is reset to that, also in place."""
+    for t, v in init["tensors"]:
+        t.copy_(v)
+    for st in opt.state.values():
+        for k, v in st.items():
+            if torch.is_tensor(v):
+                v.zero_()
+            else:
+                st[k] = 0
+    runner.set_rng_state(init["rng"])
+
 
 # algorithmic bytes per image, FrostNet-Large w=1.0 @224, int8 activations + bf16 gradients (BASELINE.md section 2)
 ALGO_BYTES_PER_IMG = 45_593_016
@@ -209,6 +266,7 @@ def side_workload(args, dev):
     torch.manual_seed(1882)
     batch = args.batch if args.batch != 512 else 256
     g = torch.Generator(device=dev).manual_seed(1882)
+    dump = {} if args.dump_outputs else None         # --dump-outputs: the outputs of the step, kept as the step (or its capture) makes them
     if args.workload in ("infer", "float"):
         model = F.MODEL_REGISTRY[f"frostnet_{args.mode}_1_0"]().to(dev)
         x = torch.randn(batch, 3, args.res, args.res, device=dev, generator=g).contiguous(memory_format=torch.channels_last)
@@ -229,6 +287,7 @@ def side_workload(args, dev):
             tgts.append(torch.cat([c - wh / 2, c + wh / 2, torch.randint(0, 20, (k, 1), generator=rng).float()], 1).to(dev))
         opt = QSGD(H.make_param_groups(model, 1e-5), lr=5e-3, momentum=0.9, nesterov=True, clip_by=1e-3, toss_coin=True, noise_decay=1e-2)
         opt.is_warmup = False
+        init = initial_state(model, model.hip_runner()) if dump is not None else None
         crit = S.MultiBoxLoss(21)
         tgts = S.pad_targets(tgts, dev)          # the collate step of a detection data loader: ragged boxes -> [N, K, 5] + validity mask
 
@@ -237,6 +296,8 @@ def side_workload(args, dev):
             loc, conf, pri = model(x)
             ll, lc = crit((loc, conf, pri), tgts)
             (ll + lc).backward()
+            if dump is not None:
+                dump.update(loc=loc, conf=conf, loss_loc=ll, loss_conf=lc)
         step = None
         # algorithmic bytes of the detector step by the headline's rule, counted from the engine's tape of one training forward: backbone
         # (Large @512: 2 139 234 304 MAC) + extras + the twelve prediction heads, every conv 1 B / element forward, bf16 gradients backward
@@ -270,13 +331,18 @@ def side_workload(args, dev):
         bytes_per_img, metric, dtype = 26_130_000, "images/sec FrostNet-Large 224x224 bf16 inference", "bf16"
         what = f"FrostNet-{args.mode.capitalize()} float model, bf16 inference (BatchNorm folded), batch={batch}, {args.res}x{args.res} NHWC (BASELINE.json config c2)"
     else:
+        init = initial_state(model, model.hip_runner()) if dump is not None else None
         model.train()
         opt = QSGD(H.make_param_groups(model, 1e-5), lr=5e-3, momentum=0.9, nesterov=True, clip_by=1e-3, toss_coin=True, noise_decay=1e-2)
         crit = torch.nn.CrossEntropyLoss()
 
         def body():                              # harness.train_one_iter without its optimizer step (helper_functions.py:139-142)
             opt.zero_grad(set_to_none=True)
-            crit(model(x), tgt).backward()
+            y = model(x)
+            loss = crit(y, tgt)
+            loss.backward()
+            if dump is not None:
+                dump.update(logits=y, loss=loss)
         step = None
         prec = model.hip_runner().precision          # activation storage: bf16 (default) or fp32 (FROST_FLOAT_PRECISION=fp32, the reference's precision)
         bytes_per_img, metric, dtype = None, "images/sec FrostNet-Large 224x224 float warm-up fwd+bwd", prec
@@ -337,10 +403,18 @@ def side_workload(args, dev):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        y = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     value = batch * args.steps / dt
+    if dump is not None:
+        if args.workload in ("infer", "int8"):
+            dump["logits"] = static_out if graphed else y
+        else:                                    # a training step: once more from the seeded state every run starts from (see main)
+            restore_state(init, opt, model.hip_runner())
+            step()
+            torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, dump)
     out = dict(metric=metric, value=round(value, 2), unit="images/sec", n_gpus=1, steps=args.steps, warmup=args.warmup,
                ms_per_step=round(dt / args.steps * 1e3, 3), higher_is_better=True, scaling="weak", vs_baseline=None, dtype=dtype,
                data="synthetic", config=dict(workload=what, per_gpu_batch=batch, resolution=args.res, hip_graph=graphed))
@@ -446,10 +520,16 @@ def main():
     ap.add_argument("--res", type=int, default=224)
     ap.add_argument("--mode", default="large")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the roofline leg (per-kernel HIP-event timing, graph census), the CPU baseline and, for N=1, the two extra legs; "
+                         "without it a run only sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline leg")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N=1 headline run: skip the two extra legs (the fp32-gradient mode's step time; the data-parallel code path on a 1-rank RCCL group)")
+                    help="--full, N=1: skip the two extra legs (the fp32-gradient mode's step time; the data-parallel code path on a 1-rank RCCL group)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the step's loss and network outputs as DIR/<name>.npy (training workloads: one more step from the "
+                         "seeded state every run starts from)")
     ap.add_argument("--buckets", type=int, default=4, help="N>1: gradient buckets = hipGraph segments of the backward pass")
     ap.add_argument("--single-allreduce", action="store_true",
                     help="N>1: one graph + ONE all-reduce after the backward instead of the bucketed, backward-overlapped default (A/B)")
@@ -507,6 +587,7 @@ def main():
     from frostnet_amd.parallel import SegmentedStep, broadcast_model
 
     torch.manual_seed(1882)                       # Classification/train.py:38-39
+    dump = {} if args.dump_outputs else None      # --dump-outputs: the outputs of the step, kept as the step (or its capture) makes them
     detect = args.workload == "detect"
     g = torch.Generator(device=dev).manual_seed(1882 + rank)
     if detect:
@@ -535,7 +616,10 @@ def main():
         mbl = S.MultiBoxLoss(21)
 
         def loss_of(xx, tt):                      # module surface: model(x) -> (loc, conf, priors) -> MultiBoxLoss (qtrainval.py:186-190)
-            ll, lc = mbl(model(xx), tt)
+            out = model(xx)
+            if dump is not None:
+                dump.update(loc=out[0], conf=out[1])
+            ll, lc = mbl(out, tt)
             return ll + lc
 
         def maps_loss(maps, tt):                  # the same loss from the twelve dequantised maps (SegmentedStep's body)
@@ -559,7 +643,10 @@ def main():
         crit = CrossEntropyLoss()                     # nn.CrossEntropyLoss semantics, forward + backward in one HIP kernel (harness.py)
 
         def loss_of(xx, tt):
-            return crit(model(xx), tt)
+            y = model(xx)
+            if dump is not None:
+                dump["logits"] = y
+            return crit(y, tt)
         seg_kw = dict(criterion=crit)
 
     # N = 1: model(x) -> loss.backward() -> optimizer.step() (the reference loop, helper_functions.py:139-143) captured as ONE hipGraph.
@@ -575,6 +662,8 @@ def main():
         opt.zero_grad(set_to_none=True)               # the reference loop (helper_functions.py:139); host-side only: p.grad = None, nothing is launched
         loss = loss_of(x, tgt)
         loss.backward(gradient=gscale)
+        if dump is not None:
+            dump["loss"] = loss
         return loss
 
     ctl = {"comm": True}                          # the exposed-communication measurement replays the step with the collectives switched off
@@ -589,6 +678,7 @@ def main():
                 dist.all_reduce(runner.grad_arena)
         opt.step()
 
+    init = initial_state(model, runner) if dump is not None else None
     for _ in range(max(1, min(args.warmup, 3))):      # first steps build tables / state before any capture
         eager_step()
     torch.cuda.synchronize()
@@ -730,6 +820,16 @@ def main():
         dt = float(t.item())
     ms = dt / args.steps * 1e3
     value = args.batch * world * args.steps / dt
+    if dump is not None:
+        # the state drifts apart between runs over the steps (fp32 atomics in the backward, fake-quant index flips): the step whose outputs are
+        # written runs from the seeded state every run starts from, on every rank (the step's collectives need them all)
+        restore_state(init, opt, runner)
+        step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            if seg is not None:
+                dump["loss"] = seg.loss
+            dump_outputs(args.dump_outputs, dump)
 
     comm = None
     if dp:
@@ -779,7 +879,7 @@ def main():
                     fallback=capture_fallback, allreduce_check=allreduce_check)
 
     roofline = None
-    if rank == 0 and not args.no_roofline and not detect:
+    if rank == 0 and args.full and not args.no_roofline and not detect:
         # per-kernel HIP-event timing on the launch stream (eager pass: events cannot be read out of a replayed graph)
         def local_step():                  # no collective in here: only rank 0 runs this leg
             crit(model(x), tgt).backward()
@@ -841,13 +941,13 @@ def main():
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and not detect:
+        if args.full and not args.no_cpu_baseline and world == 1 and not detect:
             try:
                 cpu = cpu_baseline()
             except Exception as e:  # pragma: no cover
                 cpu = dict(value=None, error=str(e))
         extras = {}
-        if world == 1 and not dp and not detect and not args.no_extras and graph is not None:
+        if args.full and world == 1 and not dp and not detect and not args.no_extras and graph is not None:
             # (1) the mode that meets north_star's 1e-3 gradient statement (FROST_GRAD=fp32: fp32 activation gradients, fp64 long sums) gets a driver-timed number
             # beside the bf16-gradient headline; (2) the N > 1 code path -- chain of hipGraph segments with the bucket's RCCL all-reduce between them -- on a 1-rank
             # RCCL group: its cost over the single graph is the segmentation + collective-launch overhead every rank pays at N = 8

@@ -255,6 +255,24 @@ def test_bench_launcher_dry_run_eight_ranks_and_failure_modes():
     assert time.time() - t0 < 200
 
 
+def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: float32 (float64 kept) .npy files; arrays over the byte budget become the same seeded sample in every run."""
+    import bench
+    a = torch.arange(1000, dtype=torch.float16).reshape(10, 100)
+    b = torch.linspace(0, 1, 200, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "all"), dict(a=a, b=b))
+    ra, rb = np.load(tmp_path / "all" / "a.npy"), np.load(tmp_path / "all" / "b.npy")
+    assert ra.dtype == np.float32 and ra.shape == (10, 100) and np.array_equal(ra, a.float().numpy())
+    assert rb.dtype == np.float64 and np.array_equal(rb, b.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1800)                       # a: 4000 B, b: 1600 B -> each keeps 1800 / 5600 of its elements
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), dict(a=a, b=b))
+    sa, sb = np.load(tmp_path / "s1" / "a.npy"), np.load(tmp_path / "s1" / "b.npy")
+    assert sa.nbytes + sb.nbytes <= 1800 and sa.size == 321 and sb.size == 64
+    assert np.array_equal(sa, np.load(tmp_path / "s2" / "a.npy")) and np.array_equal(sb, np.load(tmp_path / "s2" / "b.npy"))
+    assert np.all(np.diff(sa) > 0) and np.isin(sa, ra).all()            # distinct elements of the array, in their original order
+
+
 def _shard_oracle_worker(rank, world, port, q):
     import torch.distributed as dist
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)

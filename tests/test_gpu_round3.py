@@ -174,6 +174,33 @@ def test_bench_force_dp_runs_the_rccl_backend():
     assert all(b["allreduce_us"] > 0 for b in ga["buckets"]) and ga["step_ms_without_collectives"] > 0
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run times --steps steps and leaves what --full adds out (roofline leg, CPU baseline, extra legs).  --dump-outputs writes
+    the step's loss and logits as float32 .npy files, 64 MB at most, and two runs with the same arguments write the same arrays (the written step
+    starts from the seeded state): the logits bit for bit and the loss to rounding, even with a different number of timed steps before it."""
+    recs, dumps = [], []
+    for steps, warmup in ((3, 2), (2, 1)):
+        d = tmp_path / f"s{steps}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--batch", "64",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        recs.append(json.loads(lines[0]))
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+    rec = recs[0]
+    assert rec["steps"] == 3 and rec["warmup"] == 2 and rec["config"]["hip_graph"] is True
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] * rec["ms_per_step"] / 64e3 - 1) < 1e-2
+    assert rec["roofline"] is None and rec["cpu_baseline"] is None and "fp32_grad_ms_per_step" not in rec["config"]
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["logits", "loss"]
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["logits"].shape == (64, 1000) and a["loss"].shape == ()
+    assert np.array_equal(a["logits"], b["logits"])
+    assert abs(float(a["loss"]) - float(b["loss"])) <= 1e-5 * abs(float(a["loss"]))
+
+
 # ------------------------------------------------------------------------------------------------ epoch loops + checkpoint resume
 def _tiny_loader(n_batches, batch, res, seed):
     g = torch.Generator().manual_seed(seed)
