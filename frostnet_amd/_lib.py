@@ -38,6 +38,12 @@ class FrostFDesc(C.Structure):
                 ("kind", C.c_int32), ("cpad", C.c_int32), ("kpad", C.c_int32), ("kpad_t", C.c_int32), ("fp32", C.c_int32)]
 
 
+class FrostSSDMap(C.Structure):
+    """One prediction map of the float detector's gather / scatter (a HOST array of these is passed, include/frost_hip.h)."""
+    _fields_ = [("buf", P), ("coef", P), ("hw", C.c_int64), ("doff", C.c_int64), ("stored", C.c_int32), ("used", C.c_int32),
+                ("cpad", C.c_int32), ("which", C.c_int32)]
+
+
 ABI_VERSION = 5
 TICKET_WORDS = 40      # FROST_TICKET_WORDS: zeroed uint32 words behind every last-workgroup-done ticket (main counter + 32 sub-counters)
 
@@ -188,6 +194,10 @@ _PROTOS = {
     "frost_float_cat_f32": [P, I, P, I, L, P, P],
     "frost_float_add_f32": [P, P, L, P, P],
     "frost_float_stem_im2col_f32": [P, I, I, I, L, L, L, L, P, P],
+    "frost_float_ssd_gather": [P, I, I, L, L, P, P, P],
+    "frost_float_ssd_gather_f32": [P, I, I, L, L, P, P, P],
+    "frost_float_ssd_scatter": [P, I, I, L, L, P, P, P],
+    "frost_float_ssd_scatter_f32": [P, I, I, L, L, P, P, P],
     "frost_infer_block_ok": [I, I, I, I, I, I, I, I, I, I],
     "frost_infer_block_w_ok": [I, I, I, I, I, I, I, I, I],
     "frost_infer_block_w": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P],

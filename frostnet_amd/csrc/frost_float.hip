@@ -1571,3 +1571,114 @@ extern "C" int frost_float_stem_im2col_f32(const float* x, int n, int h, int w, 
   hipLaunchKernelGGL(k_f32_stem_im2col, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), x, n, h, w, ho, wo, sn, sc, sh, sw, out);
   return frost_check_launch("float_stem_im2col_f32");
 }
+
+// ------------------------------------------------------------------------------------------------ SSDLite detector: prediction maps <-> (loc, conf)
+// replaces: SSDLiteFrostNet._assemble (ssdlite.py) -- cat over the sources of permute(0, 2, 3, 1).reshape(n, -1) of every loc map, and of the first
+// A_k * C channels of every conf map -- and its autograd backward.  A pixel's A_k * 4 (loc) or A_k * C (conf) channels are one contiguous run in the
+// NHWC map and in the destination row of its image, so both directions copy runs: one thread = 8 channels of one pixel of one map (one 16-byte load of
+// bf16, two of fp32), all twelve maps in one launch (the work index is split by a per-map prefix table in the launch arguments).  No atomics: every
+// output element has exactly one writer, the result does not depend on the schedule.
+struct FSsdArgs {
+  FrostSSDMap m[FROST_SSD_MAX_MAPS];
+  int64_t start[FROST_SSD_MAX_MAPS + 1];        // first work unit of map k; start[nmaps] = total
+  int64_t ld[2];                                // destination row length per image: loc (P * 4), conf (P * C)
+  float* dst[2];                                // gather: loc, conf (written); scatter: dloc, dconf (read, NULL = zero gradient)
+  int nmaps;
+};
+__device__ __forceinline__ int f_ssd_map(const FSsdArgs& a, int64_t i) {
+  int k = 0;
+  while (k + 1 < a.nmaps && i >= a.start[k + 1]) ++k;
+  return k;
+}
+// gather: loc / conf fp32.  coef != NULL (training): buf holds the head's kept 1x1 conv output and its BatchNorm (linear ConvBN) is applied here,
+// y = conv * scale + bias -- the same fma as the emit pass (frost_float_ew mode 1), which therefore never runs for a head.
+template <typename ET>
+__global__ __launch_bounds__(256) void k_f_ssd_gather(const FSsdArgs a) {
+  const int64_t tot = a.start[a.nmaps];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < tot; i += (int64_t)gridDim.x * 256) {
+    const int k = f_ssd_map(a, i);
+    const FrostSSDMap& m = a.m[k];
+    const int g = (m.used + 7) >> 3;
+    const int64_t u = i - a.start[k];
+    const int ch = (int)(u % g) * 8; const int64_t r = u / g; const int64_t p = r % m.hw; const int64_t img = r / m.hw;
+    float v[8];
+    FEl<ET>::ld8((const ET*)m.buf + (img * m.hw + p) * m.stored + ch, v);       // ch + 8 <= stored (stored is a multiple of 8)
+    if (m.coef) {
+      float sc[8], bi[8];
+      FEl<float>::ld8(m.coef + FC_SCALE * m.cpad + ch, sc);
+      FEl<float>::ld8(m.coef + FC_BIAS * m.cpad + ch, bi);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = fmaf(v[e], sc[e], bi[e]);
+    }
+    float* d = a.dst[m.which] + img * a.ld[m.which] + m.doff + p * m.used + ch;
+    const int cnt = m.used - ch;
+    if (cnt >= 8 && ((uintptr_t)d & 15) == 0) {
+      FEl<float>::st8(d, v);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) if (e < cnt) d[e] = v[e];
+    }
+  }
+}
+// scatter: the gradient of every map in its storage type; channels [used, stored) of a conf map (the padding _assemble drops) get exact zeros
+template <typename ET>
+__global__ __launch_bounds__(256) void k_f_ssd_scatter(const FSsdArgs a) {
+  const int64_t tot = a.start[a.nmaps];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < tot; i += (int64_t)gridDim.x * 256) {
+    const int k = f_ssd_map(a, i);
+    const FrostSSDMap& m = a.m[k];
+    const int g = m.stored >> 3;
+    const int64_t u = i - a.start[k];
+    const int ch = (int)(u % g) * 8; const int64_t r = u / g; const int64_t p = r % m.hw; const int64_t img = r / m.hw;
+    const float* s = a.dst[m.which];
+    float v[8];
+    if (s) {
+      const float* sp = s + img * a.ld[m.which] + m.doff + p * m.used + ch;
+      const int cnt = m.used - ch;
+      if (cnt >= 8 && ((uintptr_t)sp & 15) == 0) {
+        FEl<float>::ld8(sp, v);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (e < cnt) ? sp[e] : 0.0f;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = 0.0f;
+    }
+    FEl<ET>::st8((ET*)m.buf + (img * m.hw + p) * m.stored + ch, v);
+  }
+}
+template <typename ET>
+static int float_ssd_any(bool scatter, const FrostSSDMap* maps, int nmaps, int n, int64_t ldloc, int64_t ldconf, float* loc, float* conf, hipStream_t s) {
+  FROST_REQUIRE(maps && nmaps >= 1 && nmaps <= FROST_SSD_MAX_MAPS && n >= 1, "float_ssd: 1 .. 12 maps, n >= 1");
+  FROST_REQUIRE(scatter || (loc && conf), "float_ssd_gather: loc and conf are written");
+  FSsdArgs a;
+  a.nmaps = nmaps; a.ld[0] = ldloc; a.ld[1] = ldconf; a.dst[0] = loc; a.dst[1] = conf;
+  a.start[0] = 0;
+  for (int k = 0; k < nmaps; ++k) {
+    const FrostSSDMap& m = maps[k];
+    FROST_REQUIRE(m.buf && m.hw >= 1 && m.which >= 0 && m.which <= 1, "float_ssd: map buffer, pixels, destination 0 (loc) / 1 (conf)");
+    FROST_REQUIRE(m.stored % 8 == 0 && m.used >= 1 && m.used <= m.stored, "float_ssd: stored channels a multiple of 8, 1 <= used <= stored");
+    FROST_REQUIRE(m.doff >= 0 && m.doff + m.hw * m.used <= a.ld[m.which], "float_ssd: a map's run lies outside the destination row");
+    FROST_REQUIRE(!m.coef || m.cpad >= m.stored, "float_ssd: coefficient rows narrower than the map");
+    a.m[k] = m;
+    a.start[k + 1] = a.start[k] + (int64_t)n * m.hw * (scatter ? m.stored / 8 : (m.used + 7) / 8);
+  }
+  for (int k = nmaps; k < FROST_SSD_MAX_MAPS; ++k) { a.m[k] = maps[0]; a.start[k + 1] = a.start[nmaps]; }
+  int64_t grid = (a.start[nmaps] + 255) / 256; if (grid > 2048) grid = 2048;     // 8 workgroups per CU of the 256, grid-stride beyond
+  if (scatter) hipLaunchKernelGGL(k_f_ssd_scatter<ET>, dim3((unsigned)grid), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_f_ssd_gather<ET>, dim3((unsigned)grid), dim3(256), 0, s, a);
+  return frost_check_launch(scatter ? "float_ssd_scatter" : "float_ssd_gather");
+}
+extern "C" int frost_float_ssd_gather(const FrostSSDMap* maps, int nmaps, int n, int64_t ldloc, int64_t ldconf, float* loc, float* conf, void* stream) {
+  return float_ssd_any<uint16_t>(false, maps, nmaps, n, ldloc, ldconf, loc, conf, as_stream(stream));
+}
+extern "C" int frost_float_ssd_gather_f32(const FrostSSDMap* maps, int nmaps, int n, int64_t ldloc, int64_t ldconf, float* loc, float* conf, void* stream) {
+  return float_ssd_any<float>(false, maps, nmaps, n, ldloc, ldconf, loc, conf, as_stream(stream));
+}
+extern "C" int frost_float_ssd_scatter(const FrostSSDMap* maps, int nmaps, int n, int64_t ldloc, int64_t ldconf, const float* dloc, const float* dconf, void* stream) {
+  return float_ssd_any<uint16_t>(true, maps, nmaps, n, ldloc, ldconf, (float*)dloc, (float*)dconf, as_stream(stream));
+}
+extern "C" int frost_float_ssd_scatter_f32(const FrostSSDMap* maps, int nmaps, int n, int64_t ldloc, int64_t ldconf, const float* dloc, const float* dconf, void* stream) {
+  return float_ssd_any<float>(true, maps, nmaps, n, ldloc, ldconf, (float*)dloc, (float*)dconf, as_stream(stream));
+}

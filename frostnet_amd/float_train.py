@@ -150,6 +150,7 @@ class FloatRunner:
         self.last = self._add("last_layer", model.last_layer.conv, _act_code(model.last_layer)) if hasattr(model, "last_layer") else None
         self.fc = model.classifier[2] if hasattr(model, "classifier") else None
         self.drop_rate = float(model.classifier[1].p) if self.fc is not None else 0.0
+        self._bind_extra()
         self._finish()
         self._stem_tmp = torch.zeros(self.stem.cout * 64, dtype=torch.float32, device=self.device)
 
@@ -192,6 +193,9 @@ class FloatRunner:
             self._grad_views.append(v)
             self._gv[id(p)] = v
             off += p.numel()
+
+    def _bind_extra(self):
+        """Layers a subclass binds behind the backbone (FloatSSDRunner: the SSDLite extras and heads); none for the classifier / features backbone."""
 
     def _bind_block(self, pre, blk):
         ent = dict(blk=blk, squeeze=None, conv1=None)
@@ -565,3 +569,169 @@ class FloatRunner:
             taps[bi] = t
         # blocks after the last tap (x4 -> x5 are all used; nothing is dead in the reference's backbone)
         self._trunk_bwd(None, taps)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------- SSDLite detector
+class _FloatSSDFunction(torch.autograd.Function):
+    """image -> (loc [N,P,4], conf [N,P,C]) of the float SSDLite detector; backward scatters their gradients onto the twelve maps and runs the
+    hand-written backward.  A loss that uses only one of the two hands None for the other (materialize_grads off): a zero gradient."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, runner):
+        ctx.set_materialize_grads(False)
+        heads = runner._maps_impl(x, record=True, lazy_heads=_LAZY_EMIT)
+        ctx.runner, ctx.heads = runner, heads
+        return runner._gather(heads)
+
+    @staticmethod
+    def backward(ctx, dloc, dconf):
+        heads, ctx.heads = ctx.heads, None
+        ctx.runner._backward_ssd(heads, dloc=dloc, dconf=dconf)
+        return None, None, None
+
+
+class _FloatSSDMapsFunction(torch.autograd.Function):
+    """image -> the twelve prediction maps [loc0, conf0, loc1, ...] as fp32 NCHW (SSDRunner.forward_maps' surface, for debugging)."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, runner):
+        heads = runner._maps_impl(x, record=True, lazy_heads=False)
+        ctx.runner, ctx.heads = runner, heads
+        return tuple(o.float().contiguous() for o, _ in heads)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        heads, ctx.heads, run = ctx.heads, None, ctx.runner
+        gs = []
+        for (o, _), g in zip(heads, grads):
+            t = run._new(o.n, o.h, o.w, o.c)
+            if g is None:
+                t.buf.zero_()
+            else:
+                run._store(t.buf[: o.npix * o.c], g.float().permute(0, 2, 3, 1).contiguous())
+            gs.append(t)
+        run._backward_ssd(heads, grads=gs)
+        return None, None, None
+
+
+class FloatSSDRunner(FloatRunner):
+    """frostnet_amd.ssdlite.SSDLiteFrostNet in float mode on the float kernels (the StatAssist warm-up of the detector, Object_Detection/qtrainval.py:187-238,
+    or a whole float run): backbone sources at strides 8 / 16 / 32, the SSDLite extras (1x1 -> depthwise 3x3 stride 2 -> 1x1, BN + ReLU each) and the
+    separable heads (depthwise 3x3 + BN + ReLU, 1x1 + BN), then the twelve maps gathered into (loc, conf) by one HIP launch (frost_float_ssd_gather).
+    Training: each head's 1x1 conv output is kept for its backward anyway, so the gather applies that layer's BatchNorm on load and the head emit passes
+    never run (fp32 outputs to the loss in both precisions); eval reads the emitted maps.  Backward: frost_float_ssd_scatter -> heads -> per-source sum of
+    the loc / conf head gradients and the next extra stage's -> extras in reverse -> the trunk with taps at the three backbone sources."""
+
+    def _set_precision(self, precision):
+        super()._set_precision(precision)
+        sfx = "_f32" if self.fp32 else ""
+        self._fn["ssd_gather"] = "frost_float_ssd_gather" + sfx
+        self._fn["ssd_scatter"] = "frost_float_ssd_scatter" + sfx
+
+    def _bind_extra(self):
+        m = self.model
+        self.anchors, self.num_classes = list(m.ANCHORS), int(m.num_classes)
+        self.extras = [(self._add(f"extras.{i}.pw1", e.pw1.conv, _act_code(e.pw1)), self._add(f"extras.{i}.dw", e.dw.conv, _act_code(e.dw)),
+                        self._add(f"extras.{i}.pw2", e.pw2.conv, _act_code(e.pw2))) for i, e in enumerate(m.extras)]
+        self.heads = [(self._add(f"loc.{i}.dw", l.dw.conv, _act_code(l.dw)), self._add(f"loc.{i}.pw", l.pw.conv, 0),
+                       self._add(f"conf.{i}.dw", c.dw.conv, _act_code(c.dw)), self._add(f"conf.{i}.pw", c.pw.conv, 0))
+                      for i, (l, c) in enumerate(zip(m.loc, m.conf))]
+
+    def _check_train_input(self, x):
+        """torch BatchNorm2d refuses a training forward with one value per channel; here the 1x1 tail maps would otherwise be normalised with var = 0."""
+        if x.dim() != 4 or not x.is_cuda:
+            raise ValueError("expected an (N,3,H,W) tensor on the model's device")
+        n, h, w = x.shape[0], x.shape[2], x.shape[3]
+        for l in self.layers:               # forward order; only the stride-2 layers change the map size (every one pads (k - 1) / 2)
+            if l.stride == 2:
+                h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        if n * h * w == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size torch.Size([{n}, {self.extras[-1][2].cout}, {h}, {w}])")
+
+    def forward(self, x):
+        """(loc [N,P,4], conf [N,P,C]) fp32 -- SSDLiteFrostNet._assemble of the twelve maps."""
+        if self.model.training and torch.is_grad_enabled():
+            return _FloatSSDFunction.apply(self._params[0], x, self)
+        return self._gather(self._maps_impl(x, record=False, lazy_heads=_LAZY_EMIT))
+
+    def forward_maps(self, x):
+        """The twelve maps [loc0, conf0, loc1, ...] as fp32 NCHW (conf maps with their padding channels), like SSDRunner.forward_maps."""
+        if self.model.training and torch.is_grad_enabled():
+            return list(_FloatSSDMapsFunction.apply(self._params[0], x, self))
+        return [o.float().contiguous() for o, _ in self._maps_impl(x, record=False, lazy_heads=False)]
+
+    def _maps_impl(self, x, record, lazy_heads):
+        """-> [(head output FAct, its 1x1 layer)] x 12.  lazy_heads (training): the FAct holds the 1x1 conv output, BatchNorm not yet applied."""
+        training = self.model.training
+        if training:
+            self._check_train_input(x)
+        a, outs = self._trunk(x, training, record)
+        e = self.stage_ends
+        sources = [outs[e[1]], outs[e[2]], outs[e[4]]]
+        for pw1, dw, pw2 in self.extras:           # pw1 -> dw like conv1 -> conv2 of a block: the depthwise layer applies pw1's BN + ReLU on load
+            t = self._conv(pw1, a, training, record, lazy=_LAZY_EMIT)
+            a = self._conv(pw2, self._conv(dw, t, training, record), training, record)
+            sources.append(a)
+        heads = []
+        for s, (ldw, lpw, cdw, cpw) in zip(sources, self.heads):
+            for dw, pw in ((ldw, lpw), (cdw, cpw)):
+                heads.append((self._conv(pw, self._conv(dw, s, training, record), training, record, lazy=lazy_heads), pw))
+        return heads
+
+    def _ssd_table(self, heads, grads=None):
+        """FrostSSDMap host table of the twelve maps (include/frost_hip.h) -> (table, N, P)."""
+        tab = (L.FrostSSDMap * len(heads))()
+        offs, p = [], 0
+        for k, a in enumerate(self.anchors):
+            o = heads[2 * k][0]
+            offs.append(p)
+            p += o.h * o.w * a
+        for i, (o, pw) in enumerate(heads):
+            k, which = divmod(i, 2)
+            width = 4 if which == 0 else self.num_classes
+            m = tab[i]
+            m.buf = (grads[i] if grads is not None else o).buf.data_ptr()
+            m.coef = pw.coef.data_ptr() if (grads is None and o.src is not None) else None
+            m.hw, m.doff, m.stored, m.used, m.cpad, m.which = o.h * o.w, offs[k] * width, o.c, self.anchors[k] * width, pw.cpad, which
+        return tab, heads[0][0].n, p
+
+    def _gather(self, heads):
+        tab, n, p = self._ssd_table(heads)
+        c = self.num_classes
+        loc = torch.empty(n, p, 4, dtype=torch.float32, device=self.device)
+        conf = torch.empty(n, p, c, dtype=torch.float32, device=self.device)
+        call(self._fn["ssd_gather"], tab, len(heads), n, p * 4, p * c, ptr(loc), ptr(conf), stream())
+        return loc, conf
+
+    def _sum(self, a, b):
+        s = self._new(a.n, a.h, a.w, a.c)
+        call(self._fn["add"], ptr(a.buf), ptr(b.buf), a.npix * a.c, ptr(s.buf), stream())
+        return s
+
+    def _backward_ssd(self, heads, dloc=None, dconf=None, grads=None):
+        """grads: the twelve map gradients (FAct) -- or None: scattered from dloc / dconf (fp32 [N,P,4] / [N,P,C]; None = zero)."""
+        self._begin_backward()
+        if grads is None:
+            grads = [self._new(o.n, o.h, o.w, o.c) for o, _ in heads]
+            tab, n, p = self._ssd_table(heads, grads)
+            dl = dloc.contiguous().float() if dloc is not None else None
+            dc = dconf.contiguous().float() if dconf is not None else None
+            call(self._fn["ssd_scatter"], tab, len(heads), n, p * 4, p * self.num_classes, ptr(dl), ptr(dc), stream())
+        self._keep.extend(g.buf for g in grads)         # (held until the side stream's join in _end_backward, with the heads' kept conv outputs)
+        self._keep.extend(o.buf for o, _ in heads)
+        srcg = []
+        for k, (ldw, lpw, cdw, cpw) in enumerate(self.heads):
+            gl, gc = grads[2 * k], grads[2 * k + 1]
+            d = self._conv_bwd(lpw, ptr(gl.buf), gl.c, True)
+            dl_ = self._conv_bwd(ldw, ptr(d.buf), d.c, True)
+            d = self._conv_bwd(cpw, ptr(gc.buf), gc.c, True)
+            srcg.append(self._sum(dl_, self._conv_bwd(cdw, ptr(d.buf), d.c, True)))
+        g = srcg[5]
+        for i in range(len(self.extras) - 1, -1, -1):      # extra stage i maps source i + 2 to source i + 3
+            pw1, dw, pw2 = self.extras[i]
+            d = self._conv_bwd(pw2, ptr(g.buf), g.c, True)
+            d = self._conv_bwd(dw, ptr(d.buf), d.c, True)
+            d = self._conv_bwd(pw1, ptr(d.buf), d.c, True)
+            g = self._sum(srcg[i + 2], d)
+        e = self.stage_ends
+        self._trunk_bwd(None, {e[1]: srcg[0], e[2]: srcg[1], e[4]: g})

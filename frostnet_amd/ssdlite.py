@@ -7,6 +7,9 @@ composition SURVEY N3 asks for, following the reference's conventions:
   * SSDLite form (MobileNetV2 paper, sec. 6.3): every regular conv of the SSD extras / prediction layers becomes depthwise 3x3 + pointwise 1x1 --
     exactly the two conv kinds the Frost bottleneck is made of, so the whole detector runs on the fake-quantised HIP engine
     (ConvBNReLU / ConvBN of frostnet.py:14-60, BN in every layer like the reference's `ConvBN` head layers, ssd_qmv2.py:56-77);
+  * both phases of the reference's detection recipe run on the device: the float model (the StatAssist warm-up, Object_Detection/qtrainval.py:187-238,
+    or a whole `--quant False` run) trains on the float kernels (frostnet_amd.float_train.FloatSSDRunner), then fuse_model() + prepare_qat
+    (harness.statassist_qat_switch) hands the same parameters to the fake-quant engine (frostnet_amd.runner.SSDRunner); on the CPU the stock modules run;
   * PriorBox (layers/functions/prior_box.py:28-55) and MultiBoxLoss (layers/modules/multibox_loss.py:48-117, layers/box_utils.py:71-139)
     restated in vectorised, device-agnostic torch (they are the caller's loss, not conv math) and pinned to the reference by goldens.
 Class-score maps are padded to a multiple of 8 channels (the HIP backward's channel granularity); the padding is sliced off before the loss."""
@@ -251,7 +254,11 @@ class SSDLiteFrostNet(_FrostBase):
 
     def forward(self, x):
         if x.is_cuda:
-            return self._assemble(self.hip_runner().forward_maps(x))
+            r = self.hip_runner()
+            if r.is_qat:
+                return self._assemble(r.forward_maps(x))
+            loc, conf = r.forward(x)            # the float model: (loc, conf) gathered on the device in _assemble's order
+            return loc, conf, self.priors
         x = self.conv1(self.quant(x))
         sources = []
         for i in range(5):
@@ -267,12 +274,20 @@ class SSDLiteFrostNet(_FrostBase):
         return self._assemble(maps)
 
     def hip_runner(self):
+        """The device executor: SSDRunner (fake-quant) for the QAT-prepared model, FloatSSDRunner for the float model (StatAssist warm-up / float
+        training, `float_precision` 'bf16' | 'fp32'); rebuilt when the mode, the float precision or the parameters change."""
+        qat = self._is_qat_prepared()
         r = self.__dict__.get("_hip_runner")
-        if r is None or r.model is not self or not r.still_valid():
-            if not self._is_qat_prepared():
-                raise NotImplementedError("the SSDLite detector runs on the HIP device in fake-quant (QAT-prepared) mode: fuse_model() + prepare_qat first")
-            from .runner import SSDRunner
-            r = SSDRunner(self)
-            r.is_qat = True
+        want = getattr(self, "float_precision", None)
+        if r is not None and not qat and want is not None and getattr(r, "precision", want) != want:
+            r = None
+        if r is None or r.model is not self or r.is_qat != qat or not r.still_valid():
+            if qat:
+                from .runner import SSDRunner
+                r = SSDRunner(self)
+            else:
+                from .float_train import FloatSSDRunner
+                r = FloatSSDRunner(self)
+            r.is_qat = qat
             self.__dict__["_hip_runner"] = r
         return r

@@ -40,7 +40,8 @@ extern "C" {
  *          floats, all zeroed by the caller: the fused pointwise / depthwise backward kernels spread their flush atomics over the copies, frost_weight_grad_finalize[_table]
  *          and frost_stem_wgrad_remap add them up; every other producer writes copy 0.  Larger layers keep one copy.
  *          New entries (additive): frost_step_prologue, frost_block_dw_bwd_c1 / _c1_ok, frost_hswish_converted.  The `relu` argument of the frost_float_* and
- *          frost_infer_pw / _dw / _stem entries is an activation code: 0 none, 1 ReLU, 2 hard-swish (0 / 1 mean what they meant). */
+ *          frost_infer_pw / _dw / _stem entries is an activation code: 0 none, 1 ReLU, 2 hard-swish (0 / 1 mean what they meant).
+ *          New entries (additive): frost_float_ssd_gather[_f32] / frost_float_ssd_scatter[_f32] with the FrostSSDMap table (the float SSDLite detector). */
 #ifndef FROST_DWQ_NC          /* (a -D override is a dev A/B build: the binding must be told the same value, FROST_DWQ_NC / FROST_COEF_ROWS_ALLOC / FROST_STATS_TABLES in the environment) */
 #define FROST_DWQ_NC 4
 #endif
@@ -449,6 +450,24 @@ int frost_float_head_bwd_f32(const float* dlogits, const float* pooled, const fl
 int frost_float_cat_f32(const float* a, int ca, const float* b, int cb, int64_t npix, float* y, void* stream);      /* y = cat([a, b], channels) */
 int frost_float_add_f32(const float* a, const float* b, int64_t n, float* y, void* stream);
 int frost_float_stem_im2col_f32(const float* x, int n, int h, int w, int64_t sn, int64_t sc, int64_t sh, int64_t sw, float* out, void* stream);
+/* SSDLite detector on the float path (frostnet_amd.float_train.FloatSSDRunner): the twelve NHWC prediction maps [loc0, conf0, loc1, ...] <-> loc fp32
+ * [n][ldloc] (= [N, P, 4]) and conf fp32 [n][ldconf] (= [N, P, C]) in the element order of SSDLiteFrostNet._assemble: sources in order, pixels row-major,
+ * anchors; of a pixel's `stored` channels the first `used` (A_k * 4 or A_k * C) are its run.  `maps` is a HOST array of nmaps (<= FROST_SSD_MAX_MAPS)
+ * entries, copied into the launch's arguments.  gather: buf is read; coef != NULL means buf holds the head's 1x1 conv output and y = buf * coef[c] +
+ * coef[cpad + c] (the scale / bias rows of its FrostFDesc coefficient table) is gathered.  scatter: buf is written, every stored channel: the gradient
+ * for c < used, 0 in the padding; dloc / dconf NULL = a zero gradient; coef is ignored.  Deterministic (no atomics). */
+typedef struct FrostSSDMap {
+  void* buf;             /* NHWC [n][hw][stored], bf16 (int16 storage) or fp32 (the _f32 entries)                 */
+  const float* coef;     /* gather: NULL or the coefficient table of the head's 1x1 ConvBN                            */
+  int64_t hw;            /* pixels per image                                                                          */
+  int64_t doff;          /* element offset of the map's first run in its image's destination row                      */
+  int32_t stored, used, cpad, which;   /* stored % 8 == 0, 1 <= used <= stored; which: 0 loc, 1 conf            */
+} FrostSSDMap;
+#define FROST_SSD_MAX_MAPS 12
+int frost_float_ssd_gather(const FrostSSDMap* maps, int nmaps, int n, int64_t ldloc, int64_t ldconf, float* loc, float* conf, void* stream);
+int frost_float_ssd_gather_f32(const FrostSSDMap* maps, int nmaps, int n, int64_t ldloc, int64_t ldconf, float* loc, float* conf, void* stream);
+int frost_float_ssd_scatter(const FrostSSDMap* maps, int nmaps, int n, int64_t ldloc, int64_t ldconf, const float* dloc, const float* dconf, void* stream);
+int frost_float_ssd_scatter_f32(const FrostSSDMap* maps, int nmaps, int n, int64_t ldloc, int64_t ldconf, const float* dloc, const float* dconf, void* stream);
 
 typedef struct FrostOptTensor {
   float* p; float* g; float* exp_min; float* exp_max; float* coin; float* buf0; float* buf1; float* buf2;
