@@ -12,7 +12,9 @@ composition SURVEY N3 asks for, following the reference's conventions:
     (harness.statassist_qat_switch) hands the same parameters to the fake-quant engine (frostnet_amd.runner.SSDRunner); on the CPU the stock modules run;
   * PriorBox (layers/functions/prior_box.py:28-55) and MultiBoxLoss (layers/modules/multibox_loss.py:48-117, layers/box_utils.py:71-139)
     restated in vectorised, device-agnostic torch (they are the caller's loss, not conv math) and pinned to the reference by goldens.
-Class-score maps are padded to a multiple of 8 channels (the HIP backward's channel granularity); the padding is sliced off before the loss."""
+Class-score maps are padded to a multiple of 8 channels (the HIP backward's channel granularity); the padding is sliced off before the loss.
+The test phase -- softmax, box decoding, per-class top-k and NMS (layers/functions/detection.py:14-66) -- is `Detect` / `SSDLiteFrostNet.detect`, two HIP
+kernels on the device (csrc/frost_detect.hip)."""
 import math
 import os
 
@@ -187,6 +189,112 @@ class MultiBoxLoss(nn.Module):
         return loss_l / n, loss_c / n
 
 
+_DETECT_HIP = os.environ.get("FROST_DETECT_HIP", "1") != "0"      # dev switch: the Detect layer as HIP kernels on the device (default) or as torch stages
+
+
+class Detect(nn.Module):
+    """The SSD test-phase output layer: nn.Softmax + Detect of the reference (Object_Detection/ssd_qmv2.py:290-292,320-327,
+    layers/functions/detection.py:14-66, decode: layers/box_utils.py:140-158).  forward(loc [N,P,4], conf [N,P,C] LOGITS, priors [P,4] (cx, cy, w, h)) ->
+    out [N, num_classes, top_k, 5] fp32.  For every image n and class c != bkg_label:
+      1. s_p = softmax(conf[n, p, :])[c];
+      2. box_p = decode(loc[n, p], prior_p) in the reference's operation order (cxcy = p.cxcy + l[:2] * v0 * p.wh, wh = p.wh * exp(l[2:] * v1),
+         x1y1 = cxcy - wh / 2, x2y2 = wh + x1y1);
+      3. candidates are the priors with s_p > conf_thresh (a NaN score is never a candidate);
+      4. they are ordered by score descending, EQUAL SCORES BY THE LOWER PRIOR INDEX FIRST (the reference's torch.sort leaves ties unspecified; quantised
+         models tie in quantity, so the order is defined here), and the first top_k stay;
+      5. greedy NMS in that order on box * min_dim: a candidate is kept iff its IoU with every earlier kept box is <= nms_thresh,
+         IoU = inter / (area_a + area_b - inter) with the intersection's width and height clamped at 0 (torchvision.ops.nms's rule; the reference's own
+         box_utils.nms applies the same criterion with a differently rounded union);
+      6. out[n, c, r] = (score, x1, y1, x2, y2) of the r-th kept candidate with the UNSCALED box; every other row, and the plane out[:, bkg_label], is zero.
+    detection.py:68-71 (a rank filter across classes) writes into a temporary and has no effect in the reference; it is not reproduced.
+    After a forward, `last_counts` [N, num_classes] int32 holds the number of kept rows.  No parameters, no buffers, no state_dict keys.  On the device the
+    layer is two HIP kernels (csrc/frost_detect.hip): fixed launch shapes and no host synchronisation, so it records into a HIP graph; forward_torch is the
+    CPU definition and the yardstick of tests/test_gpu_detect_post.py."""
+
+    def __init__(self, num_classes, bkg_label=0, top_k=200, conf_thresh=0.01, nms_thresh=0.45, variance=(0.1, 0.2), min_dim=512):
+        super().__init__()
+        if nms_thresh <= 0:
+            raise ValueError("nms_threshold must be non negative.")
+        if top_k < 1:
+            raise ValueError("top_k must be at least 1")
+        self.num_classes, self.bkg_label, self.top_k = int(num_classes), int(bkg_label), int(top_k)
+        self.conf_thresh, self.nms_thresh, self.variance, self.min_dim = float(conf_thresh), float(nms_thresh), tuple(variance), float(min_dim)
+        self.last_counts = None
+
+    def forward(self, loc, conf, priors):
+        priors = priors[:loc.size(1)].to(loc.device)
+        if loc.is_cuda and _DETECT_HIP:
+            return self.forward_hip(loc, conf, priors)
+        return self.forward_torch(loc, conf, priors)
+
+    def _check(self, loc, conf, priors):
+        n, p = loc.size(0), loc.size(1)
+        if loc.dim() != 3 or loc.size(2) != 4 or tuple(conf.shape) != (n, p, self.num_classes) or tuple(priors.shape) != (p, 4):
+            raise ValueError(f"Detect: loc {tuple(loc.shape)} / conf {tuple(conf.shape)} / priors {tuple(priors.shape)} are not [N,P,4] / [N,P,{self.num_classes}] / [P,4]")
+
+    @torch.no_grad()
+    def forward_hip(self, loc, conf, priors):
+        from ._lib import call, load_library, ptr, stream
+        self._check(loc, conf, priors)
+        cap = load_library().frost_detect_max_top_k()
+        if self.top_k > cap:
+            raise ValueError(f"Detect: top_k = {self.top_k} exceeds the HIP kernel's cap of {cap} (one thread per candidate of an (image, class) pair)")
+        n, p, c, dev = loc.size(0), loc.size(1), self.num_classes, loc.device
+        loc_c, conf_c, pri = loc.detach().contiguous().float(), conf.detach().contiguous().float(), priors.detach().contiguous().float()
+        scores = torch.empty(n, c, p, dtype=torch.float32, device=dev)          # class-major scores and decoded boxes: work buffers of the two kernels
+        boxes = torch.empty(n, p, 4, dtype=torch.float32, device=dev)
+        out = torch.empty(n, c, self.top_k, 5, dtype=torch.float32, device=dev)  # (every element is written by the kernel: no clearing pass)
+        counts = torch.empty(n, c, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            call("frost_detect_forward", ptr(loc_c), ptr(conf_c), ptr(pri), n, p, c, self.bkg_label, self.top_k, self.conf_thresh, self.nms_thresh,
+                 float(self.variance[0]), float(self.variance[1]), self.min_dim, ptr(scores), ptr(boxes), ptr(out), ptr(counts), stream())
+        self.last_counts = counts
+        return out
+
+    @torch.no_grad()
+    def forward_torch(self, loc, conf, priors):
+        """The layer as batched torch stages on any device: one stable sort per (image, class) row, a [K, K] IoU table, K masked steps of the greedy scan,
+        one scatter -- fixed shapes, no boolean-mask gather."""
+        self._check(loc, conf, priors)
+        loc, conf, priors = loc.float(), conf.float(), priors.float()
+        n, p, c = loc.size(0), loc.size(1), self.num_classes
+        k = min(self.top_k, p)
+        v0, v1 = self.variance
+        cxcy = priors[None, :, :2] + loc[..., :2] * v0 * priors[None, :, 2:]
+        wh = priors[None, :, 2:] * torch.exp(loc[..., 2:] * v1)
+        x1y1 = cxcy - wh / 2
+        boxes = torch.cat([x1y1, wh + x1y1], 2)                                                   # [N,P,4]
+        scores = torch.softmax(conf, 2).transpose(1, 2)                                           # [N,C,P]
+        cand = scores > self.conf_thresh                                                          # (NaN > t is False)
+        cand[:, self.bkg_label] = False
+        key = torch.where(cand, scores, scores.new_full((), -math.inf))
+        val, idx = torch.sort(key, dim=2, descending=True, stable=True)                           # stable: equal scores keep the lower prior index first
+        val, idx = val[..., :k], idx[..., :k]
+        valid = cand.gather(2, idx)                                                               # [N,C,K] (candidates sort in front of the -inf fill)
+        bx = boxes[:, None].expand(n, c, p, 4).gather(2, idx[..., None].expand(n, c, k, 4))        # [N,C,K,4]
+        sb = bx * self.min_dim
+        area = (sb[..., 2] - sb[..., 0]) * (sb[..., 3] - sb[..., 1])
+        lt = torch.max(sb[:, :, :, None, :2], sb[:, :, None, :, :2])
+        rb = torch.min(sb[:, :, :, None, 2:], sb[:, :, None, :, 2:])
+        whi = (rb - lt).clamp(min=0)
+        inter = whi[..., 0] * whi[..., 1]
+        over = ~(inter / (area[..., :, None] + area[..., None, :] - inter) <= self.nms_thresh)    # [N,C,K,K]: row i suppresses column j
+        del lt, rb, whi, inter
+        gone = ~valid
+        keep = torch.zeros_like(valid)
+        for i in range(k):                                                                        # greedy scan: K dependent, batched steps
+            ki = ~gone[..., i]
+            keep[..., i] = ki
+            gone = gone | (ki[..., None] & over[..., i, :])
+        keep &= valid
+        counts = keep.sum(2)
+        slot = torch.where(keep, keep.long().cumsum(2) - 1, torch.full_like(idx, self.top_k))     # dropped rows go to a spare slot
+        rows = torch.cat([val[..., None], bx], 3)
+        out = loc.new_zeros(n, c, self.top_k + 1, 5).scatter_(2, slot[..., None].expand(n, c, k, 5), rows)[:, :, :self.top_k].contiguous()
+        self.last_counts = counts.to(torch.int32)
+        return out
+
+
 class ExtraBlock(nn.Module):
     """SSDLite extra stage: 1x1 (-> c/2) -> depthwise 3x3 stride 2 -> 1x1 (-> c), ReLU after each (the reference applies F.relu after every
     extra layer, ssd_qmv2.py:240-243)."""
@@ -272,6 +380,21 @@ class SSDLiteFrostNet(_FrostBase):
         for s, l, c in zip(sources, self.loc, self.conf):
             maps += [self.dequant(l(s)), self.dequant(c(s))]
         return self._assemble(maps)
+
+    def detect(self, x, top_k=200, conf_thresh=0.01, nms_thresh=0.45):
+        """Detections of a batch of images: Detect(...)(*self(x)) -> [N, num_classes, top_k, 5] rows (score, x1, y1, x2, y2), the reference's test phase
+        (ssd_qmv2.py:320-327).  Eval mode only; runs without autograd; float (bf16 / fp32), QAT-prepared and hip_convert()-ed models alike.  The Detect layer
+        is built on first use and kept outside the module tree (it has no state; state_dict() is unchanged)."""
+        if self.training:
+            raise RuntimeError("SSDLiteFrostNet.detect() is the test phase: call model.eval() first")
+        key = (int(top_k), float(conf_thresh), float(nms_thresh))
+        d = self.__dict__.get("_detect")
+        if d is None or d[0] != key:
+            d = (key, Detect(self.num_classes, 0, top_k, conf_thresh, nms_thresh, tuple(self.cfg["variance"]), self.cfg["min_dim"]))
+            self.__dict__["_detect"] = d
+        with torch.no_grad():
+            loc, conf, priors = self(x)
+            return d[1](loc, conf, priors)
 
     def hip_runner(self):
         """The device executor: SSDRunner (fake-quant) for the QAT-prepared model, FloatSSDRunner for the float model (StatAssist warm-up / float

@@ -695,6 +695,16 @@ int frost_mbox_forward(const float* loc, const float* conf, const float* priors,
 int frost_mbox_backward(const float* loc, const float* conf, const float* loc_t, const int32_t* conf_t, const uint8_t* sel, const float* out, const float* g_l,
                         const float* g_c, int n, int p, int c, float* dloc, float* dconf, void* stream);
 
+/* ---- SSD Detect layer (Object_Detection/layers/functions/detection.py:14-66 behind nn.Softmax, ssd_qmv2.py:290-292,320-327) -------------------------------------
+ * frost_detect_forward: loc [n][p][4], conf [n][p][c] LOGITS, priors [p][4] (cx, cy, w, h) -> out [n][c][top_k][5] rows (score, x1, y1, x2, y2) and counts [n][c]
+ * int32 (kept rows per image and class).  Per class != bkg_label: softmax score > conf_thresh, ordered by score descending and lower prior index first among equal
+ * scores, the first top_k, greedy NMS on box * min_dim (kept iff IoU <= nms_thresh against every earlier kept box).  Every element of out and counts is written
+ * (rows past the count and the background plane as zeros).  scores [n][c][p] and boxes [n][p][4] are work buffers of the caller (contents undefined on entry).
+ * top_k: 1 .. frost_detect_max_top_k().  Two launches on `stream`, nothing synchronises with the host. */
+int frost_detect_max_top_k(void);
+int frost_detect_forward(const float* loc, const float* conf, const float* priors, int n, int p, int c, int bkg_label, int top_k, float conf_thresh,
+                         float nms_thresh, float var0, float var1, float min_dim, float* scores, float* boxes, float* out, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

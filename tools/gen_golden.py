@@ -611,6 +611,38 @@ def g11_detection():
     save("g11_detection", **out)
 
 
+# ------------------------------------------------------------------------------------------ G15 (the test phase)
+def g15_detect():
+    """The reference's test phase -- torch.softmax + Detect(21, 0, top_k, 0.01, 0.45) (Object_Detection/layers/functions/detection.py, called with loc [N,P,4] as
+    ssd_qmv2.py:320-327 does) -- on synthetic scenes that carry decision margins (tests/detect_scenes.py: the first seed whose thresholds, score gaps and IoUs
+    are all clear of their decision points in fp64).  Stored: the scene's seed and object rows (the background is regenerated from the seed), a CRC of the
+    assembled inputs, the measured margins and coverage counts, and the reference's output."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import detect_scenes as D
+    from frostnet_amd.ssdlite import prior_boxes, ssd_cfg_for
+    out = {}
+    for case, (res, N, top_k) in enumerate(((128, 3, 40), (512, 2, 200))):
+        cfg = ssd_cfg_for(res)
+        pri = prior_boxes(cfg)
+        cover = lambda m: m["pairs_over_top_k"] > 0 and m["pairs_empty"] > 0 and m["max_removed_fraction"] >= 0.3 and m["max_kept"] > 1
+        loc, conf, info = D.find_scene(pri.numpy(), N, 21, top_k, res, seed0=0, tries=32, require=cover)
+        Detect = refshim.load_detect_layer(cfg["min_dim"], cfg["variance"])
+        with torch.no_grad():
+            ref = Detect(21, 0, top_k, 0.01, 0.45).detect(T(loc), torch.softmax(T(conf), 2), pri)
+        assert tuple(ref.shape) == (N, 21, top_k, 5)
+        k = f"c{case}_"
+        out[k + "spec"] = np.array([res, N, pri.shape[0], 21, top_k, info["seed"]])
+        out[k + "obj_idx"], out[k + "obj_loc"], out[k + "obj_conf"] = info["obj_idx"], info["obj_loc"], info["obj_conf"]
+        out[k + "input_crc"] = D.crc(loc, conf, pri.numpy())
+        out[k + "margins"] = np.array([info["m_thresh"], info["m_gap"], info["m_iou"]], dtype=np.float64)
+        out[k + "coverage"] = np.array([info["pairs_over_top_k"], info["pairs_empty"], info["pairs"], info["max_kept"]])
+        out[k + "max_removed_fraction"] = np.float64(info["max_removed_fraction"])
+        out[k + "out"] = ref
+        out[k + "counts"] = (ref[..., 0] > 0).sum(2).to(torch.int32)
+        print(f"  g15 case {case}: seed {info['seed']}, {len(info['obj_idx'])} object rows, margins {out[k + 'margins']}, kept rows {int(out[k + 'counts'].sum())}")
+    save("g15_detect", **out)
+
+
 # ------------------------------------------------------------------------------------------ G12 (SURVEY N4 / Appendix E)
 def g12_fbgemm():
     """Per-channel mode = the reference's 'fbgemm' qconfig (Classification/latency_check.py:221-226), QAT flavour, version 0: activations quint8
@@ -684,8 +716,8 @@ def g8_features():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g3c", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g4t"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g3c", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g4t"]
     fns = dict(g1=g1_fake_quant, g2=g2_observer, g3=g3_layers, g3c=g3_classifier, g4=g4_blocks, g5=g5_wholenet, g6=g6_optimizers,
-               g7=g7_scalars, g8=g8_features, g9=g9_convert, g10=g10_hswish, g11=g11_detection, g12=g12_fbgemm, g13=g13_convert_fbgemm, g14=g14_hswish_converted, g4t=g4_true_shapes)
+               g7=g7_scalars, g8=g8_features, g9=g9_convert, g10=g10_hswish, g11=g11_detection, g12=g12_fbgemm, g13=g13_convert_fbgemm, g14=g14_hswish_converted, g15=g15_detect, g4t=g4_true_shapes)
     for w in which:
         fns[w]()

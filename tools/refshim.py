@@ -112,6 +112,22 @@ def load_detection():
     return PriorBox, MultiBoxLoss
 
 
+def load_detect_layer(min_dim, variance):
+    """The reference's Detect (Object_Detection/layers/functions/detection.py) for a configuration with this min_dim / variance.  torchvision is absent, so
+    its `nms_faster_rcnn` is bound to the reference's own layers.box_utils.nms over all the boxes handed in (the same keep criterion, IoU <= threshold)."""
+    load_detection()
+    import layers.functions.detection as det
+    from layers.box_utils import nms
+
+    def nms_ref(boxes, scores, thresh):
+        keep, count = nms(boxes, scores, thresh, top_k=len(boxes))
+        return keep[:count]
+
+    det.nms_faster_rcnn = nms_ref
+    det.cfg = dict(min_dim=min_dim, variance=list(variance))
+    return det.Detect
+
+
 def load_optimizer():
     if "ref_optimizer" in sys.modules:
         return sys.modules["ref_optimizer"]
