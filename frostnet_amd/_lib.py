@@ -204,6 +204,8 @@ _PROTOS = {
     "frost_infer_block_w_ok": [I, I, I, I, I, I, I, I, I],
     "frost_infer_block_w": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P],
     "frost_infer_block": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P],
+    "frost_infer_head_ok": [I, I, I, I, I],
+    "frost_infer_head": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, L, L, P, L, L, P],
     "frost_g32_wq": [P, P, P, P, P, I, I, P, P],
     "frost_g32_conv_acc": [P, P, P, I, I, I, I, I, I, I, I, I, P, P],
     "frost_g32_scratch_bytes": [],

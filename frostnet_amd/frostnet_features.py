@@ -97,6 +97,18 @@ class FrostNet(_FrostBase):
             feats = [self.dequant(f) for f in feats]
         return feats
 
+    def hip_infer_bf16(self, x):
+        """bf16 inference of the float (not QAT-prepared) backbone on the HIP inference kernels -> [x1, x2, x3, x5] as fp32 NCHW: the trunk of the
+        classifier's path (fused bottleneck kernels, BatchNorm folded once) with taps at the stage ends.  See frostnet_amd/infer.py."""
+        if self._is_qat_prepared():
+            raise RuntimeError("hip_infer_bf16 is the float model's inference path; a QAT-prepared model runs model(x)")
+        inf = self.__dict__.get("_bf16_infer")
+        if inf is None or inf.device != next(self.parameters()).device:
+            from .infer import Bf16Inference
+            inf = Bf16Inference(self)
+            self.__dict__["_bf16_infer"] = inf
+        return inf.features(x)
+
     def _freeze_stages(self):
         """frostnet_features.py:354-359: every BatchNorm2d (also the `.bn` of a fused QAT conv) goes to eval mode, i.e. normalises
         with its running statistics and stops updating them.  The QAT-prepared model honours this per layer on the HIP path (training forward in eval

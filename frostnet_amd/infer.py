@@ -6,6 +6,9 @@ pool -> (dropout is identity in eval) -> 1x1 classifier.  Here BatchNorm is fold
 (`frost_infer_weight_prep`), activations are NHWC bf16, accumulation is fp32.  Deviation from the reference: bf16 storage of
 weights and activations (the c2 configuration asks for bf16); the parity test holds the logits to the fp32 oracle within bf16
 tolerance.  No CPU / torch-eager fallback: a missing library raises.
+
+The same kernels serve the feature backbone (`Bf16Inference.features`: the trunk's stage ends) and the float SSDLite detector (`Bf16SSDInference`: trunk taps,
+the extras on the layer kernels, both prediction heads of a source in one launch of csrc/frost_ihead.hip that stores fp32 loc / conf in their final layout).
 """
 import ctypes as C
 import os
@@ -96,7 +99,8 @@ class _ILayer:
 
 
 class Bf16Inference:
-    """Binds a float FrostNet (eval mode) to the bf16 HIP inference kernels.  `__call__(x)` -> fp32 logits [N, nclass]."""
+    """Binds a float FrostNet (eval mode) to the bf16 HIP inference kernels.  `__call__(x)` -> fp32 logits [N, nclass] (a model with `last_layer` / `classifier`);
+    `features(x)` -> the stage ends [x1, x2, x3, x5] as fp32 NCHW (any FrostNet trunk)."""
 
     def __init__(self, model):
         L.load_library()
@@ -110,7 +114,7 @@ class Bf16Inference:
         self.model, self.device = model, p.device
         self.layers = []
         self.stem = self._add(model.conv1.conv, A, stem=True)
-        self.blocks = []
+        self.blocks, self.stage_ends = [], []
         for stage in (model.layer1, model.layer2, model.layer3, model.layer4, model.layer5):
             for blk in stage:
                 ent = dict(blk=blk, squeeze=None, conv1=None)
@@ -121,8 +125,11 @@ class Bf16Inference:
                 ent["conv2"] = self._add(blk.conv2.conv, A)
                 ent["reduce"] = self._add(blk.reduce_conv.conv, 0)
                 self.blocks.append(ent)
-        self.last = self._add(model.last_layer.conv, A)
-        self.fc = model.classifier[2]
+            self.stage_ends.append(len(self.blocks) - 1)
+        # the classifier's tail; the feature backbone and the detector (Bf16SSDInference) have none and bind their own layers behind the trunk
+        self.last = self._add(model.last_layer.conv, A) if hasattr(model, "last_layer") else None
+        self.fc = model.classifier[2] if hasattr(model, "classifier") else None
+        self._bind_extra()
         self._table, self._ptrs, self._versions = None, None, None
 
     def _prepare_weights(self):
@@ -146,6 +153,9 @@ class Bf16Inference:
 
     def refresh(self):
         self._versions = None
+
+    def _bind_extra(self):
+        """Layers behind the trunk that a subclass adds to the same descriptor table (one prep launch for all of them)."""
 
     def _add(self, seq, relu, stem=False):
         l = _ILayer(seq, relu, self.device, stem)
@@ -266,12 +276,14 @@ class Bf16Inference:
             ent[key] = choice
         return self._run_choice(ent, a, c, n, h, w, choice)
 
-    @torch.no_grad()
-    def __call__(self, x):
+    def _check_input(self, x):
         if self.model.training:
             raise RuntimeError("bf16 inference is the eval-mode graph: call model.eval() first")
         if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or x.device != self.device:
             raise ValueError("expected an fp32 (N,3,H,W) tensor on the model's device")
+
+    def _trunk(self, x):
+        """Stem + the five stages -> [(activation NHWC bf16, channels, h, w)] at the end of every stage (the last entry is the trunk's output)."""
         n, _, h, w = x.shape
         self._prepare_weights()
         ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
@@ -285,8 +297,32 @@ class Bf16Inference:
             call("frost_infer_stem_im2col", ptr(x), n, h, w, x.stride(0), x.stride(1), x.stride(2), x.stride(3), ptr(col), stream())
             a = self._pw(self.stem, col, npix, 64)
         c, h, w = self.stem.cout, ho, wo
-        for ent in self.blocks:
+        outs, ends = [], set(self.stage_ends)
+        for i, ent in enumerate(self.blocks):
             a, c, h, w = self._block(ent, a, c, n, h, w)
+            if i in ends:
+                outs.append((a, c, h, w))
+        return outs
+
+    @staticmethod
+    def _nchw_f32(a, n, c, h, w):
+        """NHWC bf16 activation buffer -> fp32 NCHW tensor (an output conversion, not conv math)."""
+        return a[:n * h * w * c].view(torch.bfloat16).view(n, h, w, c).permute(0, 3, 1, 2).float().contiguous()
+
+    @torch.no_grad()
+    def features(self, x):
+        """[x1, x2, x3, x5] of the feature backbone (frostnet_features.py:342-352: strides 4 / 8 / 16 / 32, x4 skipped) as fp32 NCHW."""
+        self._check_input(x)
+        outs = self._trunk(x)
+        return [self._nchw_f32(outs[i][0], x.shape[0], *outs[i][1:]) for i in (0, 1, 2, 4)]
+
+    @torch.no_grad()
+    def __call__(self, x):
+        self._check_input(x)
+        if self.last is None or self.fc is None:
+            raise RuntimeError("this model has no classifier: Bf16Inference.features(x) / Bf16SSDInference serve the backbone and the detector")
+        n = x.shape[0]
+        a, c, h, w = self._trunk(x)[-1]
         npix = n * h * w
         a, c = self._pw(self.last, a, npix, c), self.last.cout
         pooled = torch.empty(n, c, dtype=torch.float32, device=self.device)
@@ -295,3 +331,90 @@ class Bf16Inference:
         wfc = self.fc.weight.view(self.fc.out_channels, -1)
         call("frost_linear_f32", ptr(pooled), ptr(wfc), ptr(self.fc.bias), n, c, self.fc.out_channels, ptr(logits), stream())
         return logits
+
+
+# the fused prediction-head kernel (csrc/frost_ihead.hip); "0": every head as frost_infer_dw + frost_infer_pw and an fp32 placement (bf16(loc / conf) bit-identical)
+_HEAD_FUSED = os.environ.get("FROST_INFER_HEAD", "1") != "0"
+
+
+def ssd_head_offsets(anchors, map_sizes):
+    """Prior offset of every SSD source in SSDLiteFrostNet._assemble's order: source k (map h_k x w_k, A_k anchors per pixel) owns the priors
+    [poff_k, poff_k + h_k * w_k * A_k), and element j of pixel `pix` of its loc map ([.., 4 A_k] per pixel) / conf map ([.., C A_k]) sits at
+    poff_k * 4 + pix * 4 A_k + j of an image's flattened loc row / poff_k * C + pix * C A_k + j of its conf row.  map_sizes: (h, w) pairs or edge lengths."""
+    offs, p = [], 0
+    for a, m in zip(anchors, map_sizes):
+        h, w = (m, m) if isinstance(m, int) else m
+        offs.append(p)
+        p += int(h) * int(w) * int(a)
+    return offs
+
+
+class Bf16SSDInference(Bf16Inference):
+    """Binds a float SSDLiteFrostNet (eval mode) to the bf16 HIP inference kernels.  `__call__(x)` -> (loc [N,P,4], conf [N,P,C]) fp32 in _assemble's order:
+    the trunk on the fused bottleneck kernels with taps at the ends of stages 1, 2 and 4 (0-based), every extra stage as frost_infer_pw -> frost_infer_dw
+    (stride 2) -> frost_infer_pw, and ONE frost_infer_head launch per source that computes both heads and stores straight into loc / conf."""
+
+    def __init__(self, model):
+        if getattr(model, "act", "relu") == "hswish":
+            raise RuntimeError("the detector's bf16 inference path is written for ReLU networks")
+        super().__init__(model)
+
+    def _bind_extra(self):
+        m = self.model
+        self.anchors, self.num_classes = list(m.ANCHORS), int(m.num_classes)
+        self.extras = [(self._add(e.pw1.conv, 1), self._add(e.dw.conv, 1), self._add(e.pw2.conv, 1)) for e in m.extras]
+        self.heads = [(self._add(l.dw.conv, 1), self._add(l.pw.conv, 0), self._add(c.dw.conv, 1), self._add(c.pw.conv, 0)) for l, c in zip(m.loc, m.conf)]
+        self._offsets = {}
+
+    def head_offsets(self, sizes):
+        """(prior offsets, P) of the source maps `sizes`, built once per input size (host integers: the launches take them as arguments)."""
+        key = tuple(sizes)
+        hit = self._offsets.get(key)
+        if hit is None:
+            offs = ssd_head_offsets(self.anchors, sizes)
+            hit = (offs, offs[-1] + sizes[-1][0] * sizes[-1][1] * self.anchors[-1])
+            if len(self._offsets) >= 8:
+                self._offsets.pop(next(iter(self._offsets)))
+            self._offsets[key] = hit
+        return hit
+
+    def _head(self, src, layers, k, n, loc, conf, poff, p):
+        a, c, h, w = src
+        ldw, lpw, cdw, cpw = layers
+        A, C = self.anchors[k], self.num_classes
+        if _HEAD_FUSED and L.load_library().frost_infer_head_ok(h, w, c, 4 * A, C * A):
+            call("frost_infer_head", ptr(a), ptr(ldw.pack), ptr(ldw.biasf), ptr(lpw.pack), ptr(lpw.biasf), ptr(cdw.pack), ptr(cdw.biasf), ptr(cpw.pack),
+                 ptr(cpw.biasf), n, h, w, c, 4 * A, C * A, ptr(loc), p * 4, poff * 4, ptr(conf), p * C, poff * C, stream())
+            return
+        # layer launches + an fp32 placement of the used channels (geometries the fused kernel does not take; FROST_INFER_HEAD=0)
+        for dw, pw, out, width in ((ldw, lpw, loc, 4), (cdw, cpw, conf, C)):
+            t, _, _ = self._dw(dw, a, n, h, w)
+            y = self._pw(pw, t, n * h * w, c)
+            y = y[:n * h * w * pw.cout].view(torch.bfloat16).view(n, h * w, pw.cout)[:, :, :A * width]
+            out.view(n, -1)[:, poff * width:(poff + h * w * A) * width] = y.reshape(n, -1).float()
+
+    def _sources(self, x):
+        """The six source maps [(activation, channels, h, w)]: stage ends 1, 2 and 4 (0-based) of the trunk, then the output of every extra stage."""
+        n = x.shape[0]
+        outs = self._trunk(x)
+        sources = [outs[1], outs[2], outs[4]]
+        a, c, h, w = outs[4]
+        for pw1, dw, pw2 in self.extras:
+            t = self._pw(pw1, a, n * h * w, c)
+            t, h, w = self._dw(dw, t, n, h, w)
+            a, c = self._pw(pw2, t, n * h * w, pw1.cout), pw2.cout
+            sources.append((a, c, h, w))
+        return sources
+
+    def _heads(self, sources, n):
+        offs, p = self.head_offsets([(s[2], s[3]) for s in sources])
+        loc = torch.empty(n, p, 4, dtype=torch.float32, device=self.device)
+        conf = torch.empty(n, p, self.num_classes, dtype=torch.float32, device=self.device)
+        for k, (src, layers) in enumerate(zip(sources, self.heads)):
+            self._head(src, layers, k, n, loc, conf, offs[k], p)
+        return loc, conf
+
+    @torch.no_grad()
+    def __call__(self, x):
+        self._check_input(x)
+        return self._heads(self._sources(x), x.shape[0])

@@ -387,14 +387,45 @@ class SSDLiteFrostNet(_FrostBase):
         is built on first use and kept outside the module tree (it has no state; state_dict() is unchanged)."""
         if self.training:
             raise RuntimeError("SSDLiteFrostNet.detect() is the test phase: call model.eval() first")
+        d = self._detect_layer(top_k, conf_thresh, nms_thresh)
+        with torch.no_grad():
+            loc, conf, priors = self(x)
+            return d(loc, conf, priors)
+
+    def _detect_layer(self, top_k, conf_thresh, nms_thresh):
         key = (int(top_k), float(conf_thresh), float(nms_thresh))
         d = self.__dict__.get("_detect")
         if d is None or d[0] != key:
             d = (key, Detect(self.num_classes, 0, top_k, conf_thresh, nms_thresh, tuple(self.cfg["variance"]), self.cfg["min_dim"]))
             self.__dict__["_detect"] = d
+        return d[1]
+
+    def _bf16_runner(self):
+        if self._is_qat_prepared():
+            raise RuntimeError("hip_infer_bf16 is the float model's inference path; a QAT-prepared model runs model(x)")
+        inf = self.__dict__.get("_bf16_infer")
+        if inf is None or inf.device != next(self.parameters()).device:
+            from .infer import Bf16SSDInference
+            inf = Bf16SSDInference(self)
+            self.__dict__["_bf16_infer"] = inf
+        return inf
+
+    def hip_infer_bf16(self, x):
+        """bf16 inference of the float (un-fused, not QAT-prepared) detector on the HIP inference kernels -> (loc [N,P,4], conf [N,P,C], priors): eval-mode
+        BatchNorm folded once per state of the parameters, NHWC bf16 activations, fp32 accumulation, the trunk on the fused bottleneck kernels, both heads of
+        a source in one launch that stores fp32 in _assemble's order.  See frostnet_amd.infer.Bf16SSDInference."""
+        loc, conf = self._bf16_runner()(x)
+        return loc, conf, self.priors
+
+    def hip_detect_bf16(self, x, top_k=200, conf_thresh=0.01, nms_thresh=0.45):
+        """detect() on the bf16 inference path: Detect(...)(*hip_infer_bf16(x)) -> [N, num_classes, top_k, 5] with the Detect object detect() caches
+        (`last_counts` as there).  After one eager call (it measures the per-bottleneck kernel choice and folds the weights) the whole call records into a
+        HIP graph on a static input: no host synchronisation, no host-to-device copy."""
+        if self.training:
+            raise RuntimeError("bf16 inference is the eval-mode graph: call model.eval() first")
+        d = self._detect_layer(top_k, conf_thresh, nms_thresh)
         with torch.no_grad():
-            loc, conf, priors = self(x)
-            return d[1](loc, conf, priors)
+            return d(*self.hip_infer_bf16(x))
 
     def hip_runner(self):
         """The device executor: SSDRunner (fake-quant) for the QAT-prepared model, FloatSSDRunner for the float model (StatAssist warm-up / float

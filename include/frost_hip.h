@@ -375,6 +375,18 @@ int frost_infer_block(const uint16_t* x, const uint16_t* wsq, const float* bsq, 
 int frost_infer_block_w_ok(int cin, int r, int cexp, int cout, int k, int stride, int has_conv1, int th, int tw);
 int frost_infer_block_w(const uint16_t* x, const uint16_t* w1, const float* b1, const float* wdw, const float* bdw, const uint16_t* w3, const float* b3,
                         int n, int h, int w, int cin, int cexp, int cout, int k, int stride, int residual, int th, int tw, uint16_t* y, void* stream);
+/* ---- fused SSDLite prediction heads of the bf16 inference path (csrc/frost_ihead.hip) ------------------------------------------------------------
+ * replaces (eval mode, BatchNorm folded): SepHead.forward of BOTH heads of one source map (ssdlite.py: depthwise 3x3 + BN + ReLU -> 1x1 + BN) and
+ * SSDLiteFrostNet._assemble's permute / slice / cat for that source, as ONE launch.  x: NHWC bf16 [n][h][w][cin], read once for both heads.  wdw_* / bdw_*: fp32 taps
+ * [9][round_up(cin,16)] + folded bias of the depthwise layers, wpw_* / bpw_*: bf16 A-fragment packs (kpad = round_up(cin,32)) + folded biases of the 1x1 layers, all
+ * as frost_infer_weight_prep lays them out.  fp32 stores: loc[img * loc_stride + loc_off + pix * cout_loc + j], j < cout_loc, and
+ * conf[img * conf_stride + conf_off + pix * cout_conf + j], j < cout_conf (cout_conf = anchors * classes: the layer's padding channels are computed, not stored).
+ * bf16(output) is bit-identical to frost_infer_dw + frost_infer_pw.  frost_infer_head_ok: 1 if the geometry is taken (additive entries, ABI 5). */
+int frost_infer_head_ok(int h, int w, int cin, int cout_loc, int cout_conf);
+int frost_infer_head(const uint16_t* x, const float* wdw_loc, const float* bdw_loc, const uint16_t* wpw_loc, const float* bpw_loc,
+                     const float* wdw_conf, const float* bdw_conf, const uint16_t* wpw_conf, const float* bpw_conf, int n, int h, int w, int cin,
+                     int cout_loc, int cout_conf, float* loc, int64_t loc_stride, int64_t loc_off, float* conf, int64_t conf_stride,
+                     int64_t conf_off, void* stream);
 /* y[n][o] = sum_k x[n][k] * w[o][k] + bias[o], fp32 on the f32 MFMA (classifier of the float model) */
 int frost_linear_f32(const float* x, const float* w, const float* bias, int n, int k, int o, float* y, void* stream);
 
