@@ -1807,7 +1807,7 @@ extern "C" int frost_sq_emit_cat(const int8_t* x, const float* qrec_x, const int
 // A workgroup that polls for ~2^22 rounds gives up, raises ticket word 37 and emits with whatever it reads: wrong results and a test failure instead of a hung device.
 #define SQF_GEN 36
 #define SQF_ERR 37
-struct SqFwdP { SqCatP c; uint8_t* stats; uint8_t* slots; FrostFinDesc fin; int dbg; };      // dbg (FROST_SQF_DBG, timing only, wrong results): 1 = nobody waits, 2 = no fold / finalize either
+struct SqFwdP { SqCatP c; uint8_t* stats; uint8_t* slots; FrostFinDesc fin; };
 template <int KSM, int CTM>
 __global__ __launch_bounds__(256, 4) void k_sq_fwd(const SqFwdP q) {
   const SqCatP& p = q.c;
@@ -1900,7 +1900,7 @@ __global__ __launch_bounds__(256, 4) void k_sq_fwd(const SqFwdP q) {
   }
   __syncthreads();
   bool last = false;
-  if (*sflag && !(q.dbg & 2)) {                                                    // last of its sub-group: fold the group's slots, one set of atomics, then the main ticket
+  if (*sflag) {                                                    // last of its sub-group: fold the group's slots, one set of atomics, then the main ticket
     long long* g_s1 = (long long*)stats_copy(q.stats, p.cpad); unsigned long long* g_s2 = (unsigned long long*)(g_s1 + p.cpad);
     int* g_mn = (int*)(g_s2 + p.cpad); int* g_mx = g_mn + p.cpad;
     // thread = (channel, member slice): the group's ~total / 32 slots are read by 256 / r... threads side by side (one memory round trip, not one per member), LDS atomics fold the slices
@@ -1939,7 +1939,7 @@ __global__ __launch_bounds__(256, 4) void k_sq_fwd(const SqFwdP q) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's agent-scope stores have been performed
     __syncthreads();
     if (tid == 0) __hip_atomic_store(q.fin.counter + SQF_GEN, gen0 + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else if (!(q.dbg & 1)) {
+  } else {
     if (tid == 0) {
       int it = 0;
       while (__hip_atomic_load(q.fin.counter + SQF_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen0) {
@@ -2047,7 +2047,6 @@ extern "C" int frost_sq_fwd(const int8_t* x, const float* qrec_x, const int8_t* 
   const int ksm = round_up(cin, 64) / 64, ct = p.cpad / 16, ctm = ct <= 2 ? 2 : (ct <= 4 ? 4 : 6);
   p.kstr = ksm * 64 + 16;
   q.stats = (uint8_t*)stats; q.slots = (uint8_t*)slots; q.fin = *fin;
-  { static const int dbg = getenv("FROST_SQF_DBG") ? atoi(getenv("FROST_SQF_DBG")) : 0; q.dbg = dbg; }
   const size_t lds = sq_fwd_lds(cin, r);
   const dim3 grid((unsigned)((npix + 127) / 128));
   hipStream_t s = as_stream(stream);

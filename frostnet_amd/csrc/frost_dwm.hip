@@ -33,7 +33,6 @@ struct DwmP {
   const uint16_t* gout; uint16_t* dc;
   int tiles_x, tiles_y, ncb, ngrp; int nsp;      // spatial tiles (all images), channel blocks, workgroup groups per XCD
   FrostFinDesc fin; int fin_on; int sr; int cvt; float inv_count;
-  int abl;       // timing ablation (FROST_DWM_ABL; results are wrong with any bit set): 1 no global fetch, 2 no LDS staging, 4 no transpose, 8 no matrix phase, 16 no copy-out
 };
 
 // Geometry of one workgroup tile: CB channels x NSUB spatial tiles of 16 x 16 outputs (stride 1), CB * NSUB = 64.  The NSUB tiles of a
@@ -173,12 +172,11 @@ __global__ __launch_bounds__(512, 4) void k_dwm(const DwmP p) {
     for (int q = 0; q < NCH; ++q) { s1[q] = 0; s2[q] = 0.0; smn[q] = INT32_MAX; smx[q] = INT32_MIN; }
   }
   int wt = wt_lo + grp;
-  if (wt < wt_hi && !(p.abl & 1)) fetch(wt);
+  if (wt < wt_hi) fetch(wt);
   __syncthreads();
 
   for (; wt < wt_hi; wt += p.ngrp) {
     // ---- the halo tiles -> LDS, zero padding = zero-point fill
-    if (!(p.abl & 2))
 #pragma unroll
     for (int q = 0; q < NU; ++q) {
       const int u = tid + 512 * q;
@@ -189,10 +187,10 @@ __global__ __launch_bounds__(512, 4) void k_dwm(const DwmP p) {
       }
     }
     __syncthreads();
-    if (wt + p.ngrp < wt_hi && !(p.abl & 1)) fetch(wt + p.ngrp);              // lands under this tile's arithmetic
+    if (wt + p.ngrp < wt_hi) fetch(wt + p.ngrp);              // lands under this tile's arithmetic
     // ---- transpose into channel planes.  CB = 64: one transposing read = 8 pixels x 64 channels (lane = channel gets its 8 pixels);
     // CB = 32: 16 pixels x 32 channels (lane & 31 = channel, lane >> 5 = which 8 of the 16 pixels)
-    if (!(p.abl & 4)) {
+    {
       dv2i raw[NT];
 #pragma unroll
       for (int i = 0; i < NT; ++i) {
@@ -214,7 +212,6 @@ __global__ __launch_bounds__(512, 4) void k_dwm(const DwmP p) {
 
     // ---- matrix phase: per channel one B operand set, then per sub-tile 3 A operands, NM matrix instructions and the epilogue
     uint32_t pk[NSUB][4];
-    if (!(p.abl & 8))
 #pragma unroll
     for (int q = 0; q < NCH; ++q) {
       const int lc0 = (q >> 2) * 32 + 4 * w, lc = lc0 + (q & 3);         // channels past the end of a partial block run too (zero taps, zero start value; nothing of theirs is flushed or stored)
@@ -278,7 +275,7 @@ __global__ __launch_bounds__(512, 4) void k_dwm(const DwmP p) {
         }
       }
     }
-    if (EMIT && !(p.abl & 16)) {
+    if (EMIT) {
       __syncthreads();
       // copy-out: 8-byte pieces (8 channels of one pixel), coalesced along the channels
       constexpr int C8 = CB / 8;
@@ -372,7 +369,6 @@ int frost_dwm_fwd(const int8_t* x, const float* qrec_x, const int8_t* wq_pack, c
   p.pad = (k - 1) / 2; p.ho = h; p.wo = w;
   p.inv_count = 1.0f / (float)((int64_t)n * p.ho * p.wo);
   p.stats = (uint8_t*)stats; p.coef = (float*)coef; p.qy = qrec_y; p.relu = relu; p.y = y; p.cvt = (mode == 2);
-  static const int abl = getenv("FROST_DWM_ABL") ? atoi(getenv("FROST_DWM_ABL")) : 0; p.abl = abl;
   if (fin) { p.fin = *fin; p.fin_on = 1; p.coef = fin->coef; p.qy = fin->qrec_y; p.relu = fin->relu; }
   if (mode == 0) return k == 3 ? launch_dwm_cb<3, DM_STATS>(p, s) : launch_dwm_cb<5, DM_STATS>(p, s);
   if (mode == 2) return k == 3 ? launch_dwm_cb<3, DM_EMIT_CVT>(p, s) : launch_dwm_cb<5, DM_EMIT_CVT>(p, s);

@@ -970,10 +970,8 @@ static void set_tiling(PwP& p, int64_t npix, int rowbytes) {
 }
 
 // pixel-wave split of the 8 waves for a layer of CT channel tiles: 8 pixel waves x 1 channel wave up to 4 tiles, 4 x 2 up to 8, 2 x 4 above.
-// FROST_PW_WP8_CT (dev): bit mask of CT values that take 8 x 1 instead (a tile count the channel waves cannot share evenly, e.g. 9 = 3 groups of 3 for one channel wave)
+// (8 x 1 for a tile count the channel waves cannot share evenly, e.g. 9 = 3 groups of 3 for one channel wave, measured +0.10 ms per step: profiles/r06_sweep.txt)
 static int pw_wave_split(int CT) {
-  static const long wp8 = getenv("FROST_PW_WP8_CT") ? strtol(getenv("FROST_PW_WP8_CT"), nullptr, 0) : 0;
-  if (CT < 63 && ((wp8 >> CT) & 1)) return 8;
   return CT <= 4 ? 8 : (CT <= 8 ? 4 : 2);
 }
 

@@ -147,17 +147,18 @@ __global__ __launch_bounds__(256, (WG_PFD > 1) ? 2 : 3) void k_pw_wgrad(const ui
 // version needed 224 VGPRs: 8 waves per CU, latency-bound).
 #define BT 128
 #define RSD2 288   // dc rows: 128 bf16 + 32 bytes (72 dwords = 8 x 9, see RSD)
-// NB = 16-channel input tiles per wave: 2 -> a 128 x 128 (co x ci) workgroup tile, 4 -> 128 x 256.  The x tile lives in LDS as bf16 (q - zp, exact), converted ONCE per
+// NB = 16-channel input tiles per wave.  Only NB = 2 is built: a 128 x 128 (co x ci) workgroup tile.  The x tile lives in LDS as bf16 (q - zp, exact), converted ONCE per
 // element while staging -- as int8 every wave converted its own B fragments (the two co-halves twice over): 280 of the loop's ~330 VALU instructions per block, on 1 - 2
-// waves per SIMD with no MFMA overlap.  The 256-wide tile reads the dc tensor ONCE for layers with 128 < Cin <= 256 (the 7 x 7 expand convs: dc is 6 x the size of x)
-// and halves the re-reads of the narrow dc of the reduce convs (counters: 1.7x the algorithmic bytes with 128 x 128 tiles).
+// waves per SIMD with no MFMA overlap.  NB = 4 (a 128 x 256 tile, 105 KB of LDS, one workgroup per CU) read the dc tensor ONCE for layers with 128 < Cin <= 256 and
+// halved the re-reads of the narrow dc of the reduce convs (counters: 1.7x the algorithmic bytes with 128 x 128 tiles), but was slower inside the step and is no
+// longer instantiated (see frost_pw_wgrad below); the parameter and the NB-dependent launch bound stay so that the NB = 2 kernel is the code it was.
 template <int NB>
 __global__ __launch_bounds__(512, (NB == 2) ? 2 : 1) void k_pw_wgrad_big(const uint16_t* __restrict__ dc, const int8_t* __restrict__ x, const float* qx,
                                                                            int64_t npix, int cin, int cout, float* __restrict__ dwq, int nsplit, int xmap) {
   constexpr int BTI = NB * 64;                   // input channels of the workgroup tile
   constexpr int RSXB = BTI * 2 + 32;              // x rows: bf16 + 32 bytes (8 x odd dwords, like the dc rows)
   constexpr int XU = BTI / 32;                   // 8-byte x units per thread and block
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];   // [128][RSD2] + [128][RSXB]: 72 KB / 105 KB
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];   // [128][RSD2] + [128][RSXB]: 72 KB at NB = 2
   uint8_t* dcs = lds; uint8_t* xs = lds + KPIX * RSD2;
   const int tid = threadIdx.x, lane = tid & 63, i16 = lane & 15, g = lane >> 4;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -285,13 +286,11 @@ extern "C" int frost_pw_wgrad(const uint16_t* dc, const int8_t* x, const float* 
                               float* dwq, void* stream) {
   FROST_REQUIRE(cin % 8 == 0 && cout % 8 == 0, "pw_wgrad: channels must be multiples of 8");
   const int64_t nblk = (npix + KPIX - 1) / KPIX;
-  if (cin > 64 && cout > 64) {      // wide layers: 128 x 128 tiles, or 128 x 256 where that saves a pass over dc / halves the passes over a narrow dc (Cin > 128)
-    // OFF by default: alone the wider tile is faster on those layers and reads dc once, but inside the step it is SLOWER (21.22 -> 21.34 ms/step, interleaved): one 512-thread
-    // workgroup with 105 KB of LDS and ~190 registers takes a whole CU away from the main stream for as long as it runs, the 128 x 128 workgroups share theirs
-    static const int wide = getenv("FROST_WG_CI256") ? atoi(getenv("FROST_WG_CI256")) : 0;
-    // only where the wider tile adds no padded channels (Cin = 240, 1440, 1728: measured 75 -> 62, 71 -> 55, 103 -> 106 us; Cin = 288 / 312 / 624 would pad 128 more: 103 -> 140, 41 -> 53, 56 -> 66)
-    if (wide && cin > 128 && round_up(cin, 256) == round_up(cin, 128)) launch_wgb<4>(dc, x, qrec_x, npix, cin, cout, dwq, nblk, as_stream(stream));
-    else launch_wgb<2>(dc, x, qrec_x, npix, cin, cout, dwq, nblk, as_stream(stream));
+  if (cin > 64 && cout > 64) {      // wide layers: 128 x 128 tiles (k_pw_wgrad_big<2>)
+    // The 128 x 256 tile (NB = 4) is not instantiated: alone it is faster where it adds no padded channels and reads dc once (Cin = 240, 1440: 75 -> 62, 71 -> 55 us), but inside
+    // the step it is SLOWER (21.22 -> 21.34 ms/step, interleaved): one 512-thread workgroup with 105 KB of LDS and ~190 registers takes a whole CU away from the main stream for
+    // as long as it runs, the 128 x 128 workgroups share theirs
+    launch_wgb<2>(dc, x, qrec_x, npix, cin, cout, dwq, nblk, as_stream(stream));
     return frost_check_launch("pw_wgrad_big");
   }
   const int ntile = ((cout + WT - 1) / WT) * ((cin + WT - 1) / WT);

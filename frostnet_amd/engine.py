@@ -27,9 +27,7 @@ _DW_FUSE = os.environ.get("FROST_DW_FUSE", "1") != "0"     # dev switch for A/B 
 _PROLOGUE3 = os.environ.get("FROST_PROLOGUE3", "1") != "0"  # per-step prologue (sigma snapshot, weight preparation, statistics reset) as three launches over a flat workgroup map (0 = the seven table launches; bit-identical)
 _PROLOGUE3_CAP = int(os.environ.get("FROST_PROLOGUE3_CAP", "128"))  # most workgroups one layer gets (32 / 64 / 128: 19.94 / 19.87 / 19.83 ms per step, interleaved)
 _DW_BWD_ONE = os.environ.get("FROST_DW_BWD_ONE", "1") != "0"   # depthwise k = 3 stride-1 backward of the tiled (high-resolution) layers: dc + weight gradient + data gradient in one sweep (csrc/frost_dwb.hip)
-_DW_ONE_OVER_BLK = os.environ.get("FROST_DWB_OVER_BLK", "0") != "0"
 _DW_C1 = os.environ.get("FROST_DWB_C1", "3") != "0"          # ... carrying the reduce pass of the pointwise layer in front of it (stride-2 layers with Cin = 16 / 24)
-_DW_FUSE_K5 = os.environ.get("FROST_DW_FUSE_K5", "0") != "0"   # the 5x5 two-images-per-tile fused dc + wgrad variant spills 132 B of scratch: separate kernels are 0.8 % faster end to end (A/B, r2)
 _PW_KEEP = os.environ.get("FROST_PW_KEEP", "1") != "0"      # backward of the wide-K pointwise layers: one conv recomputation + element-wise reduce / dc (A/B switch)
 _FIN_FOLD = os.environ.get("FROST_FIN_FOLD", "1") != "0"    # dev switch: conv finalize folded into the statistics kernels' last workgroup
 _BLOCK_FUSE = os.environ.get("FROST_BLOCK_FUSE", "1") != "0"   # block-boundary folds: the cat's observer update rides in the squeeze's finalize tail
@@ -53,24 +51,7 @@ _STEM_FUSED_CVT = os.environ.get("FROST_STEM_CONVERTED", "1") != "0"   # convert
 _SQ_PERSIST = os.environ.get("FROST_SQ_PERSIST", "0") != "0"
 _BLOCK_SQCAT = os.environ.get("FROST_BLOCK_SQCAT", "1") != "0"      # squeeze_conv emit + cat requantisation in one launch (frost_sq_emit_cat), bit-identical to the two it replaces
 _PW_FUSE = os.environ.get("FROST_PW_FUSE", "1") != "0"     # dev switch: fused pointwise backward (dc + dgrad + wgrad in one kernel)
-_WG_PRIO = int(os.environ.get("FROST_WG_PRIO", "0"))        # priority of the weight-gradient stream(s) (torch: lower = higher priority); A/B switch
-_WG_NSTREAMS = int(os.environ.get("FROST_WG_NSTREAMS", "1"))  # weight-gradient streams taken round-robin per fork (single-GPU step only); A/B switch
-_WG_STREAM = int(os.environ.get("FROST_WG_STREAM", "1"))   # bit 0: pointwise, bit 1: depthwise weight gradients on a second stream (A/B switch)
-# depthwise weight gradients of maps no wider than this also go to the second stream.  Measured (two boxes, 2-3 runs each): 14 -> -0.2 ms, but
-# 7, 28, 56 and "only the 14x14 maps" -> +1.1 ms (the captured graph serialises differently): too close to a cliff for a default, stays off
-_DW_WG_MAXW = int(os.environ.get("FROST_DW_WG_MAXW", "0"))
-# join the weight-gradient stream back into the main stream after this many forked weight gradients (0 = only at the end of the backward).  Inside a captured
-# hipGraph ONE long side branch is not scheduled beside the layers it was forked from: the replay trace (profiles/r05_replay_nodes_*.txt) shows all 39 pointwise
-# weight gradients starting ~8 ms late, beside the bandwidth-bound 112 x 112 / 56 x 56 backward instead of the latency-bound 14 x 14 / 7 x 7 one
-_WG_JOIN = int(os.environ.get("FROST_WG_JOIN", "0"))
-# FROST_WG_DEFER = H > 0: the pointwise weight gradients of layers on maps of height <= H are not forked one by one but collected and launched on the side stream
-# behind ONE fork when the backward reaches a larger map (their dc / x buffers stay referenced until the join, as before).  Measured (profiles/r05_wgrad_schedule.txt):
-# H = 14 is 0.33 ms SLOWER than per-layer forks (21.63 vs 21.30 ms/step) -- in the captured step the per-layer forks already start ~8 ms late, and starting all of
-# them 1.8 ms earlier (beside layer3.0 / layer2.1's backward) costs more than the 39 fork gaps of ~4.6 us it removes.  0 = fork per layer (default).
-_WG_DEFER = int(os.environ.get("FROST_WG_DEFER", "0"))
-# FROST_WG_BATCH = N > 1: one fork per N pointwise weight gradients (each fork costs the main stream a ~4.6 us gap in the captured step): the weight gradients of N
-# consecutive layers are launched on the side stream together, right after the dc pass of the N-th (A/B switch; 0 / 1 = fork per layer)
-_WG_BATCH = int(os.environ.get("FROST_WG_BATCH", "0"))
+_WG_STREAM = os.environ.get("FROST_WG_STREAM", "1") != "0"   # pointwise weight gradients of the non-fused layers on a second stream (0 = on the main stream, as under the per-kernel profiler)
 # skip_add's backward folded into the element-wise reduce / dc passes of the reduce_conv that produced its second operand (frost_pw_ew_add_bwd): one launch less per
 # residual block of the 14 x 14 / 7 x 7 stages and no materialised gout for that layer; bit-identical to the two launches it replaces (A/B switch)
 _ADD_BWD_FUSE = os.environ.get("FROST_ADD_BWD_FUSE", "1") != "0"
@@ -216,7 +197,10 @@ class Engine:
         self.tape = []
         self._table = None
         self.on_layer_grads = None     # callback(layer) after a layer's parameter gradients are final (DP overlap)
-        self._side, self._keep = None, []
+        self._wgmap = None             # the step prologue's flat workgroup map (built with the tables)
+        # the weight-gradient side stream (created by the first backward that uses it), `_side` = that stream while a backward forks onto it, and the buffers
+        # its launches read, kept referenced until the join (_fork_wgrad / _join_wgrad)
+        self._wg_stream, self._side, self._keep = None, None, []
         # fp32-GRADIENT parity mode (csrc/frost_g32.hip; `model.grad_precision = "fp32"` / FROST_GRAD=fp32): activation gradients and dc in fp32, long sums in
         # fp64, plain kernels -- the reference's fp32 autograd precision instead of bf16 storage.  10-30 x slower; for parity statements, not for training runs.
         self.grad_fp32 = os.environ.get("FROST_GRAD", "bf16").lower() == "fp32"
@@ -236,7 +220,7 @@ class Engine:
         if self._table is not None:
             return
         n = len(self.layers)
-        self._wgmaps = {}
+        self._wgmap = None
         arr = (L.FrostWDesc * n)()
         for i, l in enumerate(self.layers):
             arr[i] = l.desc()
@@ -254,38 +238,28 @@ class Engine:
         ptrs = (C.c_void_p * n)(*[l.sigma.data_ptr() for l in self.layers])
         self._sigma_ptrs = L.struct_to_tensor(ptrs, self.device)
 
-    def begin_step(self, observe=True, part=None):
+    def begin_step(self, observe=True):
         """Per-step prologue: BN-fold + weight fake-quant + packing for every layer (3 launches), sigma_r snapshot,
-        integer-stat reset.  Must run before the first conv of a forward pass (uses running_var BEFORE its update).
-        part = (lo, hi): only the layers [lo, hi) of the table (registration order = forward order) -- the runner prepares the few small layers of the
-        high-resolution stages first and the rest (where the parameters are) on a second stream under them; every layer must be covered before it runs."""
+        integer-stat reset.  Must run before the first conv of a forward pass (uses running_var BEFORE its update)."""
         self._ensure_tables()
         n = len(self.layers)
-        lo, hi = (0, n) if part is None else (max(0, int(part[0])), min(n, int(part[1])))
-        if hi > lo and _PROLOGUE3:
+        if n and _PROLOGUE3:
             # three launches over a flat workgroup map (a layer gets workgroups in proportion to its weights) instead of seven launches of nlayers x 8 ... 256 mostly idle ones
-            m = hi - lo
-            maps = self.__dict__.setdefault("_wgmaps", {})
-            if (lo, hi) not in maps:
+            if self._wgmap is None:
                 rows = []
-                for i, l in enumerate(self.layers[lo:hi]):
+                for i, l in enumerate(self.layers):
                     nsl = max(1, min(_PROLOGUE3_CAP, -(-l.w.numel() // 2048)))
                     rows += [[i, sl, nsl, 0] for sl in range(nsl)]
-                maps[(lo, hi)] = torch.tensor(rows, dtype=torch.int32, device=self.device)
-            wg = maps[(lo, hi)]
-            call("frost_step_prologue", C.c_void_p(self._table.data_ptr() + lo * C.sizeof(L.FrostWDesc)), m, ptr(wg), wg.shape[0],
-                 C.c_void_p(self._sigma_ptrs.data_ptr() + 8 * lo), ptr(self._stats), C.c_void_p(self._cpads.data_ptr() + 4 * lo),
-                 C.c_void_p(self._offs.data_ptr() + 8 * lo), self.rule127, 1 if observe else 0, stream(),
-                 prof=("weight_prep", sum(4 * l.w.numel() + l.wq_pack.numel() for l in self.layers[lo:hi])))
-        elif hi > lo:
-            m = hi - lo
-            tab = C.c_void_p(self._table.data_ptr() + lo * C.sizeof(L.FrostWDesc))
-            call("frost_save_sigma", tab, C.c_void_p(self._sigma_ptrs.data_ptr() + 8 * lo), m, stream())
-            call("frost_weight_prep", tab, m, max(l.w.numel() for l in self.layers[lo:hi]), self.rule127, 1 if observe else 0, stream(),
-                 prof=("weight_prep", sum(4 * l.w.numel() + l.wq_pack.numel() for l in self.layers[lo:hi])))
-            call("frost_stats_init_table", ptr(self._stats), C.c_void_p(self._cpads.data_ptr() + 4 * lo), C.c_void_p(self._offs.data_ptr() + 8 * lo), m, stream())
-        if lo == 0:
-            self.tape = []
+                self._wgmap = torch.tensor(rows, dtype=torch.int32, device=self.device)
+            wg = self._wgmap
+            call("frost_step_prologue", ptr(self._table), n, ptr(wg), wg.shape[0], ptr(self._sigma_ptrs), ptr(self._stats), ptr(self._cpads), ptr(self._offs),
+                 self.rule127, 1 if observe else 0, stream(), prof=("weight_prep", sum(4 * l.w.numel() + l.wq_pack.numel() for l in self.layers)))
+        elif n:
+            call("frost_save_sigma", ptr(self._table), ptr(self._sigma_ptrs), n, stream())
+            call("frost_weight_prep", ptr(self._table), n, max(l.w.numel() for l in self.layers), self.rule127, 1 if observe else 0, stream(),
+                 prof=("weight_prep", sum(4 * l.w.numel() + l.wq_pack.numel() for l in self.layers)))
+            call("frost_stats_init_table", ptr(self._stats), ptr(self._cpads), ptr(self._offs), n, stream())
+        self.tape = []
 
     # ------------------------------------------------------------------------------------------ helpers
     def new_act(self, n, h, w, c, q):
@@ -723,21 +697,14 @@ class Engine:
         # Pointwise weight gradients run on a second stream: nothing downstream needs them until the finalize at the end of the
         # backward, and the short low-resolution kernels leave launch gaps and tails that an independent kernel can fill.
         # Off when per-layer gradients are awaited (data parallel) and while the per-kernel profiler times the main stream.
+        # One side stream, one fork per non-fused pointwise layer right after its dc pass (_fork_wgrad), one join per gradient bucket and at the end (_join_wgrad).
         self._side = None
         if _WG_STREAM and self.on_layer_grads is None and L.PROFILER is None and self.device.type == "cuda":
-            if getattr(self, "_wg_stream", None) is None:
-                self._wg_stream = torch.cuda.Stream(device=self.device, priority=_WG_PRIO)
-                self._wg_extra = [torch.cuda.Stream(device=self.device, priority=_WG_PRIO) for _ in range(max(0, _WG_NSTREAMS - 1))]
-            # several weight-gradient streams only in the single-GPU step: a bucketed backward joins ONE side stream per bucket (decided per backward, not
-            # once at the first one -- an eager single-GPU backward followed by a bucketed one must not keep round-robining)
-            self._wg_more = self._wg_extra if boundaries is None else []
+            if self._wg_stream is None:
+                self._wg_stream = torch.cuda.Stream(device=self.device)
             self._side = self._wg_stream
             self._side.wait_stream(torch.cuda.current_stream())          # after the dwq arena fill
-            for st in self._wg_more:
-                st.wait_stream(torch.cuda.current_stream())
             self._keep = []
-            self._forks = 0
-            self._deferred = []
         rtape = list(reversed(self.tape))
         for ti, entry in enumerate(rtape):
             kind = entry[0]
@@ -814,14 +781,9 @@ class Engine:
                     call("frost_add_bwd", ptr(y.grad), ptr(a.buf), ptr(a.q), ptr(b.buf), ptr(b.q), a.numel, ptr(y.q), ptr(ga),
                          fa, ptr(gb), fb, stream(), prof=("add_bwd", 8 * a.numel))
                 y.grad = None
-        self._flush_deferred_wgrads()
-        if self._side is not None:
-            torch.cuda.current_stream().wait_stream(self._wg_stream)          # join: every weight gradient is accumulated
-            for st in getattr(self, "_wg_more", []):
-                torch.cuda.current_stream().wait_stream(st)
-            self._side = None
+        self._join_wgrad()          # every weight gradient is accumulated
+        self._side = None
         self._finalize_pending()
-        self._keep = []
         self.tape = []
 
     def _mixed_entry(self, entry):
@@ -978,25 +940,27 @@ class Engine:
             self._gtables = {}
         self._dwq_arena.zero_()
 
-    def _flush_deferred_wgrads(self, fork=True):
-        """Launch the collected pointwise weight gradients of the low-resolution stages on the side stream behind one fork (`fork=False`: the caller forks right after)."""
-        todo, self._deferred = getattr(self, "_deferred", None) or [], []
-        if not todo or self._side is None:
-            return
-        ev = torch.cuda.Event()                    # (fork=False: the caller forks again right after -- these launches still need their own dependency on the main stream)
+    def _fork_wgrad(self, *bufs):
+        """Stream handle for a weight-gradient launch that nothing needs before the join: the side stream, made to wait for the current point of the main stream
+        (the layer's dc pass), with the buffers the launch reads kept referenced until the join -- the caching allocator must not hand them to a later layer
+        while the side stream still reads them.  Without a side stream (data parallel with per-layer callbacks, per-kernel profiler, FROST_WG_STREAM=0): the main stream."""
+        if self._side is None:
+            return stream()
+        ev = torch.cuda.Event()
         ev.record()
         self._side.wait_event(ev)
-        sw = C.c_void_p(self._side.cuda_stream)
-        for dc, x, l, ynum in todo:
-            call("frost_pw_wgrad", ptr(dc), ptr(x.buf), ptr(x.q), x.npix, x.c, l.cout, ptr(l.dwq), sw, prof=("pw_wgrad", 2 * ynum + x.numel))
+        self._keep.append(bufs)
+        return C.c_void_p(self._side.cuda_stream)
+
+    def _join_wgrad(self):
+        """The main stream waits for every forked weight gradient; their buffers are released."""
+        if self._side is not None:
+            torch.cuda.current_stream().wait_stream(self._side)
+            self._keep = []
 
     def _close_bucket(self, index, on_bucket):
         """Every layer of gradient bucket `index` has run its backward: join the weight-gradient stream, finalize, notify."""
-        self._flush_deferred_wgrads()
-        if self._side is not None:
-            for st in [self._wg_stream] + list(getattr(self, "_wg_more", [])):
-                torch.cuda.current_stream().wait_stream(st)
-            self._keep = []
+        self._join_wgrad()
         self._finalize_pending(slot=index)
         if on_bucket is not None:
             on_bucket(index)
@@ -1030,210 +994,182 @@ class Engine:
             if p is not None and p.grad is None:
                 p.grad = torch.zeros_like(p)
 
+    @staticmethod
+    def _pw_fused(l, x):
+        """True iff this pointwise / stem layer's backward is the fused kernel (dc + data gradient + weight gradient in one launch): where it has an instance, and only on
+        maps of at least _PW_FUSE_MINMAP pixels per image -- below, dc + data gradient with the weight gradient on the second stream are faster."""
+        return bool(l.kind in ("pw", "stem") and _PW_FUSE and L.load_library().frost_pw_bwd_fused_ok(x.npix, x.c, l.cout) and (l.kind == "stem" or x.h * x.w >= _PW_FUSE_MINMAP))
+
     def _ew_backward(self, l, x):
-        """True iff this layer's backward runs its reduce / dc passes element-wise over the kept integer conv output (the rule of _conv_backward)."""
-        fused = l.kind in ("pw", "stem") and _PW_FUSE and bool(L.load_library().frost_pw_bwd_fused_ok(x.npix, x.c, l.cout)) and (l.kind == "stem" or x.h * x.w >= _PW_FUSE_MINMAP)
-        return bool(_PW_KEEP and not fused and l.kind == "pw" and x.c > 256 and l.cout < x.c and not getattr(l, "frozen", False))
+        """True iff this layer's backward runs its reduce / dc passes element-wise over the kept integer conv output (the rule of _pw_backward)."""
+        return bool(_PW_KEEP and not self._pw_fused(l, x) and l.kind == "pw" and x.c > 256 and l.cout < x.c and not getattr(l, "frozen", False))
+
+    def _dc_buffer(self, y, needed=True):
+        """The layer's dc tensor (bf16 bits), or None where the kernel keeps dc on chip."""
+        dc = torch.empty(y.numel + 64, dtype=torch.int16, device=self.device) if needed else None
+        if getattr(self, "_dbg", False):
+            self._last_dc = dc
+        return dc
 
     def _conv_backward(self, l, x, y, nxt=None):
         self._ensure_grad(l)
+        if l.kind == "dw":
+            self._dw_backward(l, x, y, nxt)
+        elif l.kind in ("pw", "stem"):
+            self._pw_backward(l, x, y)
+        self._after_conv_backward(l, stream())
+        y.grad = None
+
+    def _pw_backward(self, l, x, y):
+        """Pointwise / stem layer: reduce pass, then either the fused kernel or dc pass + data gradient + weight gradient (the latter on the side stream)."""
         gout = y.grad
         s = stream()
-        if _WG_DEFER and getattr(self, "_deferred", None) and x.h > _WG_DEFER:
-            self._flush_deferred_wgrads()
-        if _WG_JOIN and self._side is not None and getattr(self, "_forks", 0) >= _WG_JOIN:
-            for st in [self._wg_stream] + list(getattr(self, "_wg_more", [])):      # short side branches: the weight gradients forked so far (on every side stream) must be done before this layer starts
-                torch.cuda.current_stream().wait_stream(st)
-            self._forks = 0
-        fused = l.kind in ("pw", "stem") and _PW_FUSE and bool(L.load_library().frost_pw_bwd_fused_ok(x.npix, x.c, l.cout)) and (l.kind == "stem" or x.h * x.w >= _PW_FUSE_MINMAP)
-        blk_dw = (l.kind == "dw" and _BLOCK_DWBWD and (x.h <= 7 or _BLOCK_DWBWD >= 2) and (x.grad is None or not x.needs_grad)
-                  and bool(L.load_library().frost_block_dw_bwd_supported(x.h, x.w, l.k, l.stride, x.c)))      # dc stays in LDS there: no buffer
-        if blk_dw and _DW_ONE_OVER_BLK and x.needs_grad and x.grad is None and L.load_library().frost_dw_bwd_fused_ok(x.h, x.w, x.c, l.k, l.stride):
-            blk_dw = False          # A/B: the strip-streaming kernel instead of the image-resident one where both have an instance (FROST_DWB_MINW lets it take small maps)
-        dw_one = (l.kind == "dw" and not blk_dw and _DW_BWD_ONE and x.needs_grad and x.grad is None
-                  and bool(L.load_library().frost_dw_bwd_fused_ok(x.h, x.w, x.c, l.k, l.stride)))                 # dc stays in registers there: no buffer
-        dc = None if (fused or blk_dw or dw_one) else torch.empty(y.numel + 64, dtype=torch.int16, device=self.device)
-        if getattr(self, "_dbg", False):
-            self._last_dc = dc
-        if l.kind in ("pw", "stem"):
-            dwq_final = l.dwq
-            if l.kind == "stem":
-                l.dwq, dwq_final = l.dwq_col, l.dwq
-            args = (ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.wt_pack), ptr(l.qw), x.npix, x.c, l.cout)
-            # wide-K layers (Cin > 256: x rows too long for k_pw's DMA tile): ONE recomputation of the integer conv output on the stand-alone GEMM kernel,
-            # then the reduce and dc passes element-wise over it (N << K here: the int32 output is smaller than x) instead of two chunked k_pw passes
-            cint = None
-            if _PW_KEEP and not fused and l.kind == "pw" and x.c > 256 and l.cout < x.c:
-                cint = getattr(y, "cint", None)          # kept by the training forward; otherwise (forward without statistics) one recomputation here
-                if cint is None:
-                    cint = torch.empty(y.numel + 64, dtype=torch.int32, device=self.device)
-                    call("frost_pw_conv_int", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), x.npix, x.c, l.cout, ptr(cint), s,
-                         prof=("pw_bwd_reduce", x.numel + 4 * y.numel))
-                y.cint = None
-                ab = getattr(y, "add_bwd", None)
-                if ab is not None:          # + skip_add's backward: g = the add's gradient inside the add's STE window; the residual branch's gradient leaves here
-                    call("frost_pw_ew_add_bwd", ptr(cint), x.npix, l.cout, ptr(l.coef), ptr(l.qy), int(l.relu), 0, ptr(ab[0]), ptr(ab[1].buf), ptr(ab[1].q), ptr(y.buf),
-                         ptr(ab[2]), ptr(ab[3]), ab[4], None, s, prof=("pw_bwd_reduce", 10 * y.numel))
-                else:
-                    call("frost_pw_ew", ptr(cint), x.npix, l.cout, ptr(l.coef), ptr(l.qy), int(l.relu), 0, ptr(gout), None, s,
-                         prof=("pw_bwd_reduce", 6 * y.numel))
+        fused = self._pw_fused(l, x)
+        dc = self._dc_buffer(y, not fused)
+        dwq_final = l.dwq
+        if l.kind == "stem":
+            l.dwq, dwq_final = l.dwq_col, l.dwq
+        args = (ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.wt_pack), ptr(l.qw), x.npix, x.c, l.cout)
+        # wide-K layers (Cin > 256: x rows too long for k_pw's DMA tile): ONE recomputation of the integer conv output on the stand-alone GEMM kernel,
+        # then the reduce and dc passes element-wise over it (N << K here: the int32 output is smaller than x) instead of two chunked k_pw passes
+        cint = None
+        if _PW_KEEP and not fused and l.kind == "pw" and x.c > 256 and l.cout < x.c:
+            cint = getattr(y, "cint", None)          # kept by the training forward; otherwise (forward without statistics) one recomputation here
+            if cint is None:
+                cint = torch.empty(y.numel + 64, dtype=torch.int32, device=self.device)
+                call("frost_pw_conv_int", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), x.npix, x.c, l.cout, ptr(cint), s,
+                     prof=("pw_bwd_reduce", x.numel + 4 * y.numel))
+            y.cint = None
+            ab = getattr(y, "add_bwd", None)
+            if ab is not None:          # + skip_add's backward: g = the add's gradient inside the add's STE window; the residual branch's gradient leaves here
+                call("frost_pw_ew_add_bwd", ptr(cint), x.npix, l.cout, ptr(l.coef), ptr(l.qy), int(l.relu), 0, ptr(ab[0]), ptr(ab[1].buf), ptr(ab[1].q), ptr(y.buf),
+                     ptr(ab[2]), ptr(ab[3]), ab[4], None, s, prof=("pw_bwd_reduce", 10 * y.numel))
             else:
-                # algorithmic bytes: x 1 B/el, gradients 2 B/el (bf16)
-                pwc = (not fused) and l.kind == "pw" and bool(L.load_library().frost_pwc_bwd_ok(x.npix, x.c, l.cout))      # wide layers: chunked kernel, full-line gout / dc I/O
-                if getattr(y, "bred_done", False):          # squeeze_conv: S1 / S2 were accumulated by the cat's backward launch (frost_sq_bwd_cat)
-                    y.bred_done = False
-                elif pwc and x.npix <= _PWC_RED_MAXPIX:       # (per 64-pixel tile a pair of float atomics per channel: above ~100 k pixels k_pw's fatter tiles win -- measured 98 vs 186 us at 28 x 28)
-                    call("frost_pwc_conv_bwd", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), x.npix, x.c, l.cout, 0, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), None, s,
-                         prof=("pw_bwd_reduce", x.numel + 2 * y.numel))
-                else:
-                    call("frost_pw_conv_bwd", *args, 0, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), None, None, 0, s,
-                         prof=("pw_bwd_reduce", x.numel + 2 * y.numel))
-            self._frozen_after_reduce(l)
-            if fused:
-                # dc pass + data gradient + weight gradient in one kernel: the dc tile never leaves LDS (layers with Cout*Cin <= ~19 k)
-                gx, acc = self._grad_slot(x) if x.needs_grad else (None, 0)
-                call("frost_pw_conv_bwd_fused", *args, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), ptr(gx), acc, ptr(l.dwq), s,
-                     prof=("pw_bwd_fused", x.numel + 2 * y.numel + (2 * x.numel if x.needs_grad else 0)))
-                if l.kind == "stem":
-                    l.dwq = dwq_final
-                    call("frost_stem_wgrad_remap", ptr(l.dwq_col), l.cout, l.cin_g, ptr(l.dwq), s)
-                self._after_conv_backward(l, s)
-                y.grad = None
-                return
-            if cint is not None and getattr(y, "add_bwd", None) is not None:
-                ab = y.add_bwd
-                call("frost_pw_ew_add_bwd", ptr(cint), x.npix, l.cout, ptr(l.coef), ptr(l.qy), int(l.relu), 1, ptr(ab[0]), ptr(ab[1].buf), ptr(ab[1].q), ptr(y.buf),
-                     ptr(ab[2]), None, 0, ptr(dc), s, prof=("pw_bwd_dc", 10 * y.numel))
-                y.add_bwd = None
-            elif cint is not None:
-                call("frost_pw_ew", ptr(cint), x.npix, l.cout, ptr(l.coef), ptr(l.qy), int(l.relu), 1, ptr(gout), ptr(dc), s,
-                     prof=("pw_bwd_dc", 8 * y.numel))
-            elif pwc:
-                call("frost_pwc_conv_bwd", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), x.npix, x.c, l.cout, 1, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), s,
-                     prof=("pw_bwd_dc", x.numel + 4 * y.numel))
+                call("frost_pw_ew", ptr(cint), x.npix, l.cout, ptr(l.coef), ptr(l.qy), int(l.relu), 0, ptr(gout), None, s,
+                     prof=("pw_bwd_reduce", 6 * y.numel))
+        else:
+            # algorithmic bytes: x 1 B/el, gradients 2 B/el (bf16)
+            pwc = (not fused) and l.kind == "pw" and bool(L.load_library().frost_pwc_bwd_ok(x.npix, x.c, l.cout))      # wide layers: chunked kernel, full-line gout / dc I/O
+            if getattr(y, "bred_done", False):          # squeeze_conv: S1 / S2 were accumulated by the cat's backward launch (frost_sq_bwd_cat)
+                y.bred_done = False
+            elif pwc and x.npix <= _PWC_RED_MAXPIX:       # (per 64-pixel tile a pair of float atomics per channel: above ~100 k pixels k_pw's fatter tiles win -- measured 98 vs 186 us at 28 x 28)
+                call("frost_pwc_conv_bwd", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), x.npix, x.c, l.cout, 0, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), None, s,
+                     prof=("pw_bwd_reduce", x.numel + 2 * y.numel))
             else:
-                call("frost_pw_conv_bwd", *args, 1, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), None, 0, s,
-                     prof=("pw_bwd_dc", x.numel + 4 * y.numel))
-            defer_wg = bool(_WG_DEFER and self._side is not None and (_WG_STREAM & 1) and l.kind == "pw" and x.h <= _WG_DEFER)
-            if _WG_BATCH > 1 and self._side is not None and (_WG_STREAM & 1) and l.kind == "pw":
-                defer_wg = True
-                if len(self._deferred) + 1 >= _WG_BATCH:          # this layer completes a batch: its dc is done, flush the earlier ones now and this one below
-                    self._wg_flush_after = True
-            if self._side is not None and (_WG_STREAM & 1) and not defer_wg:      # fork right after the dc pass: the weight gradient runs beside dgrad and what follows
-                self._flush_deferred_wgrads(fork=False)
-                ev = torch.cuda.Event()
-                ev.record()
-                self._forks = getattr(self, "_forks", 0) + 1
-                if getattr(self, "_wg_more", None):          # several weight-gradient streams: the next one takes this fork
-                    allst = [self._wg_stream] + self._wg_more
-                    self._side = allst[self._forks % len(allst)]
-                self._side.wait_event(ev)
-            if x.needs_grad:
-                gx, acc = self._grad_slot(x)
-                if l.kind == "pw" and L.load_library().frost_pw_dgrad_wide_ok(x.npix, x.c, l.cout):
-                    # long dc rows (Cout > 128): a plain bf16 GEMM kernel of its own, dc fragments straight from memory, weight stages through LDS
-                    call("frost_pw_dgrad_wide", ptr(dc), ptr(l.wt_pack), ptr(l.qw), x.npix, x.c, l.cout, ptr(gx), acc, s,
-                         prof=("pw_dgrad", 2 * y.numel + 2 * x.numel))
-                else:
-                    call("frost_pw_conv_bwd", *args, 2, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), ptr(gx), acc, s,
-                         prof=("pw_dgrad", 2 * y.numel + 2 * x.numel))
-            sw = s
-            if self._side is not None and (_WG_STREAM & 1):      # dc (and x) stay referenced until the join
-                self._keep.append((dc, x.buf))
-                sw = C.c_void_p(self._side.cuda_stream)
-            if defer_wg:
-                self._deferred.append((dc, x, l, y.numel))
-                if getattr(self, "_wg_flush_after", False):
-                    self._wg_flush_after = False
-                    self._flush_deferred_wgrads()
-            else:
-                call("frost_pw_wgrad", ptr(dc), ptr(x.buf), ptr(x.q), x.npix, x.c, l.cout, ptr(l.dwq), sw,
-                     prof=("pw_wgrad", 2 * y.numel + x.numel))
+                call("frost_pw_conv_bwd", *args, 0, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), None, None, 0, s,
+                     prof=("pw_bwd_reduce", x.numel + 2 * y.numel))
+        self._frozen_after_reduce(l)
+        if fused:
+            # dc pass + data gradient + weight gradient in one kernel: the dc tile never leaves LDS (layers with Cout*Cin <= ~19 k)
+            gx, acc = self._grad_slot(x) if x.needs_grad else (None, 0)
+            call("frost_pw_conv_bwd_fused", *args, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), ptr(gx), acc, ptr(l.dwq), s,
+                 prof=("pw_bwd_fused", x.numel + 2 * y.numel + (2 * x.numel if x.needs_grad else 0)))
             if l.kind == "stem":
                 l.dwq = dwq_final
-                call("frost_stem_wgrad_remap", ptr(l.dwq_col), l.cout, l.cin_g, ptr(l.dwq), sw)
-        elif l.kind == "dw":
-            args = (ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.qw), x.n, x.h, x.w, x.c, l.k, l.stride)
-            blk = _BLOCK_DWBWD and (x.h <= 7 or _BLOCK_DWBWD >= 2) and L.load_library().frost_block_dw_bwd_supported(x.h, x.w, l.k, l.stride, x.c)
-            blk_reduce = blk          # (the image-resident reduce pass stays even when the strip-streaming kernel takes the rest: FROST_DWB_OVER_BLK)
-            blk = blk and (blk_dw or not dw_one)
-            if blk_reduce and _BLOCK_DWBRED:
-                call("frost_block_dw_bwd_reduce", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), x.n, x.h, x.w, x.c, l.k, ptr(l.coef), ptr(l.qy), int(l.relu),
-                     ptr(gout), s, prof=("blk_dw_bred", x.numel + 2 * y.numel))
+                call("frost_stem_wgrad_remap", ptr(l.dwq_col), l.cout, l.cin_g, ptr(l.dwq), s)
+            return
+        if cint is not None and getattr(y, "add_bwd", None) is not None:
+            ab = y.add_bwd
+            call("frost_pw_ew_add_bwd", ptr(cint), x.npix, l.cout, ptr(l.coef), ptr(l.qy), int(l.relu), 1, ptr(ab[0]), ptr(ab[1].buf), ptr(ab[1].q), ptr(y.buf),
+                 ptr(ab[2]), None, 0, ptr(dc), s, prof=("pw_bwd_dc", 10 * y.numel))
+            y.add_bwd = None
+        elif cint is not None:
+            call("frost_pw_ew", ptr(cint), x.npix, l.cout, ptr(l.coef), ptr(l.qy), int(l.relu), 1, ptr(gout), ptr(dc), s,
+                 prof=("pw_bwd_dc", 8 * y.numel))
+        elif pwc:
+            call("frost_pwc_conv_bwd", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), x.npix, x.c, l.cout, 1, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), s,
+                 prof=("pw_bwd_dc", x.numel + 4 * y.numel))
+        else:
+            call("frost_pw_conv_bwd", *args, 1, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), None, 0, s,
+                 prof=("pw_bwd_dc", x.numel + 4 * y.numel))
+        sw = self._fork_wgrad(dc, x.buf)          # fork right after the dc pass: the weight gradient runs beside dgrad and what follows
+        if x.needs_grad:
+            gx, acc = self._grad_slot(x)
+            if l.kind == "pw" and L.load_library().frost_pw_dgrad_wide_ok(x.npix, x.c, l.cout):
+                # long dc rows (Cout > 128): a plain bf16 GEMM kernel of its own, dc fragments straight from memory, weight stages through LDS
+                call("frost_pw_dgrad_wide", ptr(dc), ptr(l.wt_pack), ptr(l.qw), x.npix, x.c, l.cout, ptr(gx), acc, s,
+                     prof=("pw_dgrad", 2 * y.numel + 2 * x.numel))
             else:
-                call("frost_dw_conv_bwd", *args, 0, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), None, s,
-                     prof=("dw_bwd_reduce", x.numel + 2 * y.numel))
-            self._frozen_after_reduce(l)
-            gslot = self._grad_slot(x) if x.needs_grad else (None, 0)
-            c1b = nxt[1] if (blk and not gslot[1] and _BLOCK_C1 and x.needs_grad and nxt is not None and nxt[0] == "conv" and nxt[3] is x) else None
-            if (c1b is not None and c1b.kind == "pw" and c1b.k == 1 and not getattr(c1b, "frozen", False) and not c1b.per_channel and getattr(c1b, "hswish", None) is None
-                    and L.load_library().frost_block_dw_bwd_c1_ok(x.h, x.w, l.k, l.stride, x.c, nxt[2].c)):
-                # ... and the launch carries the reduce pass of the pointwise layer that produced x (conv1 of the bottleneck): conv1's integer output is recomputed per
-                # (image, chunk) on the matrix cores and its S1 / S2 accumulate from the fp32 dx values, so conv1's backward starts at its dc pass (x.bred_done)
-                x0 = nxt[2]
-                call("frost_block_dw_bwd_c1", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.qw), ptr(l.wscale) if l.per_channel else None, x.n, x.h, x.w, x.c,
-                     l.k, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(gslot[0]), ptr(l.dwq),
-                     ptr(x0.buf), ptr(x0.q), ptr(c1b.wq_pack), ptr(c1b.wsum), ptr(c1b.coef), x0.c, int(c1b.relu), s,
-                     prof=("blk_dw_bwd", x.numel + 2 * y.numel + 2 * x.numel + x0.numel))
-                x.bred_done = True
-                self._after_conv_backward(l, s)
-                y.grad = None
-                return
-            if blk and not gslot[1]:
-                # 14x14 / 7x7 maps: the image's dc lives in an LDS plane; weight gradient and data gradient come from it (csrc/frost_block.hip)
-                call("frost_block_dw_bwd", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.qw), ptr(l.wscale) if l.per_channel else None, x.n, x.h, x.w, x.c,
-                     l.k, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(gslot[0]) if x.needs_grad else None, ptr(l.dwq), s,
-                     prof=("blk_dw_bwd", x.numel + 2 * y.numel + (2 * x.numel if x.needs_grad else 0)))
-                self._after_conv_backward(l, s)
-                y.grad = None
-                return
-            c1 = nxt[1] if (dw_one and _DW_C1 and nxt is not None and nxt[0] == "conv" and nxt[3] is x) else None
-            if (c1 is not None and c1.kind == "pw" and not getattr(c1, "frozen", False) and not c1.per_channel and getattr(c1, "hswish", None) is None and not gslot[1]
-                    and L.load_library().frost_dw_bwd_fused_c1_ok(x.h, x.w, x.c, l.k, l.stride, nxt[2].c)):
-                # ... and the sweep carries the reduce pass of the pointwise layer that produced x (conv1 of the bottleneck): its S1 / S2 accumulate from the dx values as they
-                # are formed, so conv1's backward starts at its dc pass (x.bred_done) and the gradient tensor is read once instead of twice
-                x0 = nxt[2]
-                call("frost_dw_bwd_fused_c1", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.qw), ptr(l.wscale) if l.per_channel else None, x.n, x.h, x.w, x.c,
-                     l.k, l.stride, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(gslot[0]), ptr(l.dwq),
-                     ptr(x0.buf), ptr(x0.q), ptr(c1.wq_pack), ptr(c1.wsum), ptr(c1.coef), x0.c, int(c1.relu), s,
-                     prof=("dw_bwd_one", x.numel + 2 * y.numel + 2 * x.numel + x0.numel))
-                x.bred_done = True
-                self._after_conv_backward(l, s)
-                y.grad = None
-                return
-            if dw_one and not gslot[1]:
-                # dc never leaves registers: the strip-streaming kernel computes weight gradient and data gradient from it in the same sweep
-                call("frost_dw_bwd_fused", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.qw), ptr(l.wscale) if l.per_channel else None, x.n, x.h, x.w, x.c,
-                     l.k, l.stride, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(gslot[0]), ptr(l.dwq), s,
-                     prof=("dw_bwd_one", x.numel + 2 * y.numel + 2 * x.numel))
-                self._after_conv_backward(l, s)
-                y.grad = None
-                return
-            # dc pass + weight gradient in one sweep where the kernel's register state allows it (the library applies the same
-            # rule and would otherwise run the two kernels itself; calling them separately keeps the profiler tags per kernel)
-            if _DW_FUSE and l.stride == 1 and (l.k == 3 or (l.k == 5 and y.w <= 8 and _DW_FUSE_K5)):
-                call("frost_dw_conv_bwd_dc_wgrad", *args, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), ptr(l.dwq), s,
-                     prof=("dw_bwd_dc", 2 * x.numel + 4 * y.numel))
-            else:
-                call("frost_dw_conv_bwd", *args, 1, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), s,
-                     prof=("dw_bwd_dc", x.numel + 4 * y.numel))
-                # (stays on the main stream by default: beside the pointwise weight gradients it slows everything down -- measured -5 %)
-                sw = s
-                if self._side is not None and ((_WG_STREAM & 2) or y.w <= _DW_WG_MAXW):
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    self._side.wait_event(ev)
-                    self._keep.append((dc, x.buf))
-                    sw = C.c_void_p(self._side.cuda_stream)
-                call("frost_dw_wgrad", ptr(dc), ptr(x.buf), ptr(x.q), x.n, x.h, x.w, x.c, l.k, l.stride, ptr(l.dwq), sw,
-                     prof=("dw_wgrad", 2 * y.numel + x.numel))
-            if x.needs_grad:
-                gx, acc = gslot
-                call("frost_dw_dgrad", ptr(dc), ptr(l.wq_pack), ptr(l.qw), x.n, x.h, x.w, x.c, l.k, l.stride, ptr(gx), acc,
-                     ptr(l.wscale) if l.per_channel else None, s,
-                     prof=("dw_dgrad", 2 * y.numel + 2 * x.numel))
-        self._after_conv_backward(l, s)
-        y.grad = None
+                call("frost_pw_conv_bwd", *args, 2, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), ptr(gx), acc, s,
+                     prof=("pw_dgrad", 2 * y.numel + 2 * x.numel))
+        call("frost_pw_wgrad", ptr(dc), ptr(x.buf), ptr(x.q), x.npix, x.c, l.cout, ptr(l.dwq), sw,
+             prof=("pw_wgrad", 2 * y.numel + x.numel))
+        if l.kind == "stem":
+            l.dwq = dwq_final
+            call("frost_stem_wgrad_remap", ptr(l.dwq_col), l.cout, l.cin_g, ptr(l.dwq), sw)
+
+    def _dw_backward(self, l, x, y, nxt):
+        """Depthwise layer: reduce pass, then the kernel that keeps dc on chip where one has an instance (image-resident plane in LDS, or the strip-streaming sweep), else
+        dc pass + weight gradient + data gradient.  All of it on the main stream: depthwise weight gradients beside the pointwise ones slow everything down (measured -5 %)."""
+        gout = y.grad
+        s = stream()
+        lib = L.load_library()
+        blk = bool(_BLOCK_DWBWD and (x.h <= 7 or _BLOCK_DWBWD >= 2) and lib.frost_block_dw_bwd_supported(x.h, x.w, l.k, l.stride, x.c))      # the image-resident kernels have an instance
+        blk_dw = blk and (x.grad is None or not x.needs_grad)          # ... and the data gradient is written, not accumulated: dc stays in LDS there, no buffer
+        dw_one = (not blk_dw and _DW_BWD_ONE and x.needs_grad and x.grad is None
+                  and bool(lib.frost_dw_bwd_fused_ok(x.h, x.w, x.c, l.k, l.stride)))                 # dc stays in registers there: no buffer
+        dc = self._dc_buffer(y, not (blk_dw or dw_one))
+        args = (ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.qw), x.n, x.h, x.w, x.c, l.k, l.stride)
+        if blk and _BLOCK_DWBRED:
+            call("frost_block_dw_bwd_reduce", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), x.n, x.h, x.w, x.c, l.k, ptr(l.coef), ptr(l.qy), int(l.relu),
+                 ptr(gout), s, prof=("blk_dw_bred", x.numel + 2 * y.numel))
+        else:
+            call("frost_dw_conv_bwd", *args, 0, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), None, s,
+                 prof=("dw_bwd_reduce", x.numel + 2 * y.numel))
+        self._frozen_after_reduce(l)
+        gslot = self._grad_slot(x) if x.needs_grad else (None, 0)
+        c1b = nxt[1] if (blk_dw and _BLOCK_C1 and x.needs_grad and nxt is not None and nxt[0] == "conv" and nxt[3] is x) else None
+        if (c1b is not None and c1b.kind == "pw" and c1b.k == 1 and not getattr(c1b, "frozen", False) and not c1b.per_channel and getattr(c1b, "hswish", None) is None
+                and lib.frost_block_dw_bwd_c1_ok(x.h, x.w, l.k, l.stride, x.c, nxt[2].c)):
+            # ... and the launch carries the reduce pass of the pointwise layer that produced x (conv1 of the bottleneck): conv1's integer output is recomputed per
+            # (image, chunk) on the matrix cores and its S1 / S2 accumulate from the fp32 dx values, so conv1's backward starts at its dc pass (x.bred_done)
+            x0 = nxt[2]
+            call("frost_block_dw_bwd_c1", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.qw), ptr(l.wscale) if l.per_channel else None, x.n, x.h, x.w, x.c,
+                 l.k, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(gslot[0]), ptr(l.dwq),
+                 ptr(x0.buf), ptr(x0.q), ptr(c1b.wq_pack), ptr(c1b.wsum), ptr(c1b.coef), x0.c, int(c1b.relu), s,
+                 prof=("blk_dw_bwd", x.numel + 2 * y.numel + 2 * x.numel + x0.numel))
+            x.bred_done = True
+            return
+        if blk_dw:
+            # 14x14 / 7x7 maps: the image's dc lives in an LDS plane; weight gradient and data gradient come from it (csrc/frost_block.hip)
+            call("frost_block_dw_bwd", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.qw), ptr(l.wscale) if l.per_channel else None, x.n, x.h, x.w, x.c,
+                 l.k, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(gslot[0]) if x.needs_grad else None, ptr(l.dwq), s,
+                 prof=("blk_dw_bwd", x.numel + 2 * y.numel + (2 * x.numel if x.needs_grad else 0)))
+            return
+        c1 = nxt[1] if (dw_one and _DW_C1 and nxt is not None and nxt[0] == "conv" and nxt[3] is x) else None
+        if (c1 is not None and c1.kind == "pw" and not getattr(c1, "frozen", False) and not c1.per_channel and getattr(c1, "hswish", None) is None and not gslot[1]
+                and lib.frost_dw_bwd_fused_c1_ok(x.h, x.w, x.c, l.k, l.stride, nxt[2].c)):
+            # ... and the sweep carries the reduce pass of the pointwise layer that produced x (conv1 of the bottleneck): its S1 / S2 accumulate from the dx values as they
+            # are formed, so conv1's backward starts at its dc pass (x.bred_done) and the gradient tensor is read once instead of twice
+            x0 = nxt[2]
+            call("frost_dw_bwd_fused_c1", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.qw), ptr(l.wscale) if l.per_channel else None, x.n, x.h, x.w, x.c,
+                 l.k, l.stride, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(gslot[0]), ptr(l.dwq),
+                 ptr(x0.buf), ptr(x0.q), ptr(c1.wq_pack), ptr(c1.wsum), ptr(c1.coef), x0.c, int(c1.relu), s,
+                 prof=("dw_bwd_one", x.numel + 2 * y.numel + 2 * x.numel + x0.numel))
+            x.bred_done = True
+            return
+        if dw_one and not gslot[1]:
+            # dc never leaves registers: the strip-streaming kernel computes weight gradient and data gradient from it in the same sweep
+            call("frost_dw_bwd_fused", ptr(x.buf), ptr(x.q), ptr(l.wq_pack), ptr(l.wsum), ptr(l.qw), ptr(l.wscale) if l.per_channel else None, x.n, x.h, x.w, x.c,
+                 l.k, l.stride, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(gslot[0]), ptr(l.dwq), s,
+                 prof=("dw_bwd_one", x.numel + 2 * y.numel + 2 * x.numel))
+            return
+        # dc pass + weight gradient in one sweep where the kernel's register state allows it (the library applies the same
+        # rule and would otherwise run the two kernels itself; calling them separately keeps the profiler tags per kernel).
+        # k = 3 only: the 5x5 two-images-per-tile variant spills 132 B of scratch, separate kernels are 0.8 % faster end to end (A/B, r2)
+        if _DW_FUSE and l.stride == 1 and l.k == 3:
+            call("frost_dw_conv_bwd_dc_wgrad", *args, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), ptr(l.dwq), s,
+                 prof=("dw_bwd_dc", 2 * x.numel + 4 * y.numel))
+        else:
+            call("frost_dw_conv_bwd", *args, 1, ptr(l.coef), ptr(l.qy), int(l.relu), ptr(gout), ptr(dc), s,
+                 prof=("dw_bwd_dc", x.numel + 4 * y.numel))
+            call("frost_dw_wgrad", ptr(dc), ptr(x.buf), ptr(x.q), x.n, x.h, x.w, x.c, l.k, l.stride, ptr(l.dwq), s,
+                 prof=("dw_wgrad", 2 * y.numel + x.numel))
+        if x.needs_grad:
+            gx, acc = gslot
+            call("frost_dw_dgrad", ptr(dc), ptr(l.wq_pack), ptr(l.qw), x.n, x.h, x.w, x.c, l.k, l.stride, ptr(gx), acc,
+                 ptr(l.wscale) if l.per_channel else None, s,
+                 prof=("dw_dgrad", 2 * y.numel + 2 * x.numel))
 
     def _frozen_after_reduce(self, l):
         """Backward of a layer whose BatchNorm is frozen (eval form, running statistics): y = c + (beta - rm * gamma / sigma_r), so dc = gy -- the

@@ -562,3 +562,58 @@ def test_eval_prequant_logits(engine, mode, res):
     self_diff = relerr(qs2.raw_logits, raw_ref)
     print(f"[{mode}@{res}] eval pre-fake-quant logits rel-err vs oracle: {e:.2e}  (oracle 1 thread vs 16 threads: {self_diff:.2e})")
     assert e <= max(1e-2, 3 * self_diff), (e, self_diff)
+
+
+WG_STREAM_BOUND = 4 * 7.97e-5     # 4 x the larger of the two differences measured before the change under test (see test_weight_gradient_stream_does_not_change_the_step)
+
+
+def _small64_train_step(side_stream):
+    """One training forward + backward of a freshly bound FrostNet-Small @64, B = 4 (the same synthetic state every call: identical parameters, observers and
+    running statistics), with the weight-gradient side stream on or off; returns (the C-ABI entries launched, {parameter name: gradient}, whether the engine
+    created its side stream, i.e. whether this backward forked)."""
+    from frostnet_amd import frostnet as F, _lib as L, engine as EN
+    cfg = O.net_cfg("small", 1.0)
+    spec = O.float_state_spec(cfg)
+    model = F.MODEL_REGISTRY["frostnet_quant_small_1_0"](drop_rate=0.0)
+    model.load_state_dict(O.synth_state([k for k, _ in spec], [s for _, s in spec], 5000))
+    F.qat_prepare(model, version=0)
+    model.cuda().train()
+    x = T(O.synth((4, 3, 64, 64), 17)).cuda()
+    old = EN._WG_STREAM
+    EN._WG_STREAM = side_stream
+    L.CALL_LOG = []
+    try:
+        torch.nn.functional.cross_entropy(model(x), torch.tensor([3, 997, 41, 500], device="cuda")).backward()
+        torch.cuda.synchronize()
+        log = list(L.CALL_LOG)
+    finally:
+        L.CALL_LOG = None
+        EN._WG_STREAM = old
+    grads = {n: p.grad.detach().double().cpu() for n, p in model.named_parameters() if p.grad is not None}
+    return log, grads, model.hip_runner().E._wg_stream is not None
+
+
+def test_weight_gradient_stream_does_not_change_the_step(engine):
+    """The pointwise weight gradients of the non-fused layers run on a side stream, forked behind each layer's dc pass and joined at the end of the backward
+    (Engine._fork_wgrad / _join_wgrad); their dc and x buffers must stay referenced until that join, or the caching allocator hands them to a later layer while
+    the side stream still reads them.  QAT FrostNet-Small @64, B = 4, one training step through the runner with the side stream on and off: from layer2 on every
+    map is under 400 pixels per image (non-fused: dc, data gradient, forked frost_pw_wgrad), the stem and layer1 take the fused kernel -- both branches of the
+    decision in one step.  The two runs launch the same entries in the same order, and every parameter gradient agrees norm-wise.
+
+    The bound: kernels, launch shapes and stochastic-rounding seeds are the same in both runs; only the order of the float atomics and the overlap differ.
+    Measured on the commit before the scheduling experiments were removed (largest per-parameter relative difference): (a) two repeats of the stream-on step
+    2.06e-5 (layer1.0.reduce_conv's dbeta, a sum that cancels to ~0); (b) stream-on against stream-off 7.97e-5 (the stem's dgamma; two stream-off repeats differ by
+    7.93e-5 as well, and the other on / off pairing by 2.06e-5: run-to-run variation of the fused kernels' atomics, not of the stream).  Bound = 4 x the larger =
+    3.19e-4 (the margin covers atomic-order variation between devices)."""
+    torch.set_num_threads(16)
+    log_on, g_on, forked_on = _small64_train_step(True)
+    log_off, g_off, forked_off = _small64_train_step(False)
+    assert forked_on and not forked_off, "the stream-on step must run its weight gradients on the side stream, the stream-off step must not create one"
+    assert log_on == log_off, [(i, a, b) for i, (a, b) in enumerate(zip(log_on, log_off)) if a != b][:5]
+    assert "frost_pw_wgrad" in log_on and "frost_pw_conv_bwd_fused" in log_on
+    assert g_on.keys() == g_off.keys() and len(g_on) > 100
+    errs = {n: relerr(g_on[n], g_off[n]) for n in g_on}
+    worst = max(errs, key=errs.get)
+    print(f"[small@64 train, B=4] side stream on vs off: {len(log_on)} launches ({log_on.count('frost_pw_wgrad')} forked weight gradients, "
+          f"{log_on.count('frost_pw_conv_bwd_fused')} fused layers); worst gradient difference {errs[worst]:.2e} ({worst})")
+    assert errs[worst] <= WG_STREAM_BOUND, (worst, errs[worst])
