@@ -105,6 +105,9 @@ _PROTOS = {
     "frost_mbox_backward": [P, P, P, P, P, P, P, P, I, I, I, P, P, P],
     "frost_detect_max_top_k": [],
     "frost_detect_forward": [P, P, P, I, I, I, I, I, F, F, F, F, F, P, P, P, P, P],
+    "frost_voc_update": [P, P, P, P, P, I, I, I, I, I, F, F, I, I, L, P, P, P],
+    "frost_voc_ap": [P, P, I, L, I, I, P, P, P],
+    "frost_voc_reset": [P, P, I, L, P],
     "frost_stats_init_table": [P, P, P, I, P],
     "frost_pw_conv_fwd": [P, P, P, P, L, I, I, I, P, P, P, I, P, P],
     "frost_pw_conv_fwd_fin": [P, P, P, P, L, I, I, P, P, P],

@@ -9,6 +9,8 @@
   * `train` / `val` -- the epoch loops, helper_functions.py:99-163 / 306-350: mean over the iterations of the per-batch loss / top-1 / top-5.  `val`
     only switches to `model.eval()` -- as in the reference the observers stay live and keep moving with validation data.
     The running sums stay on the device: ONE host read per epoch instead of the reference's three `.item()` per iteration.
+  * `val_detector` -- the detector's validation pass, Object_Detection/qeval_convert.py:348-396 (`test_net`) as qtrainval.py:314 calls it: detections on the
+    device, scored by a `VOCEvaluator` whose state stays on the device; ONE host read per evaluation instead of one per image and class.
   * `checkpoint_state` / `save_checkpoint` / `load_checkpoint` -- Classification/train.py:193-223, helper_functions.py:400-407: the reference's
     dictionary keys, plus `hip_rng` (dropout Philox seed + draw count; the GradBoost stream resumes from the optimizer's step count).
 """
@@ -149,6 +151,33 @@ def val(val_loader, model, criterion):
     observer that has not been disabled explicitly keeps updating, exactly as the reference's val() leaves them."""
     model.eval()
     return _epoch(val_loader, model, criterion, None, 0, None, None, False)
+
+
+def val_detector(loader, model, evaluator, top_k=200, conf_thresh=0.01, nms_thresh=0.45):
+    """One validation pass of the detector: `model.eval()`, then for every (images, gt [N, G, 5], difficult [N, G], valid [N, G], sizes [N, 2] or None) of the
+    loader (ssdlite.pad_targets / voc_eval.pad_difficult turn ragged targets into these) the detections [N, C, top_k, 5] go into `evaluator.update` -- from
+    `model.hip_detect_bf16` when the model is the float detector on the device, from `model.detect` otherwise.  Returns (mean AP, per-class AP list) after the
+    evaluation's single read of the results; the evaluator is reset first and keeps the evaluation's state (counts, records) afterwards."""
+    model.eval()
+    dev = _device_of(model)
+    is_qat = getattr(model, "_is_qat_prepared", None)
+    bf16 = dev.type == "cuda" and hasattr(model, "hip_detect_bf16") and not (is_qat() if is_qat is not None else False) \
+        and not getattr(model, "_hip_converted", False)
+    evaluator.reset()
+    n = 0
+    for images, gt, difficult, valid, sizes in loader:
+        x = images.to(dev, non_blocking=True)
+        det = model.hip_detect_bf16(x, top_k, conf_thresh, nms_thresh) if bf16 else model.detect(x, top_k, conf_thresh, nms_thresh)
+        evaluator.update(det, gt.to(dev, non_blocking=True), difficult.to(dev, non_blocking=True), valid.to(dev, non_blocking=True),
+                         None if sizes is None else sizes.to(dev, non_blocking=True))
+        n += 1
+    if n == 0:
+        raise ValueError("empty loader")
+    out = evaluator.compute(check_overflow=False)
+    vals = torch.cat([evaluator.overflowed().double().reshape(1), out["mean_ap"].reshape(1), out["ap"]]).tolist()          # the evaluation's single device -> host read
+    if vals[0] != 0:
+        raise RuntimeError(evaluator.OVERFLOW_MSG)
+    return vals[1], vals[2:]
 
 
 def checkpoint_state(model, optimizer, epoch, **scalars):

@@ -41,7 +41,8 @@ extern "C" {
  *          and frost_stem_wgrad_remap add them up; every other producer writes copy 0.  Larger layers keep one copy.
  *          New entries (additive): frost_step_prologue, frost_block_dw_bwd_c1 / _c1_ok, frost_hswish_converted.  The `relu` argument of the frost_float_* and
  *          frost_infer_pw / _dw / _stem entries is an activation code: 0 none, 1 ReLU, 2 hard-swish (0 / 1 mean what they meant).
- *          New entries (additive): frost_float_ssd_gather[_f32] / frost_float_ssd_scatter[_f32] with the FrostSSDMap table (the float SSDLite detector). */
+ *          New entries (additive): frost_float_ssd_gather[_f32] / frost_float_ssd_scatter[_f32] with the FrostSSDMap table (the float SSDLite detector).
+ *          New entries (additive): frost_voc_update / frost_voc_ap / frost_voc_reset (the PASCAL VOC mean-AP evaluator). */
 #ifndef FROST_DWQ_NC          /* (a -D override is a dev A/B build: the binding must be told the same value, FROST_DWQ_NC / FROST_COEF_ROWS_ALLOC / FROST_STATS_TABLES in the environment) */
 #define FROST_DWQ_NC 4
 #endif
@@ -716,6 +717,22 @@ int frost_mbox_backward(const float* loc, const float* conf, const float* loc_t,
 int frost_detect_max_top_k(void);
 int frost_detect_forward(const float* loc, const float* conf, const float* priors, int n, int p, int c, int bkg_label, int top_k, float conf_thresh,
                          float nms_thresh, float var0, float var1, float min_dim, float* scores, float* boxes, float* out, int32_t* counts, void* stream);
+
+/* ---- PASCAL VOC average precision (Object_Detection/qeval_convert.py:177-396: test_net's gather, voc_eval, voc_ap) ----------------------------------------------
+ * Evaluator state, owned by the caller: records [c][capacity] uint64 (score bits << 32 | (~ordinal & 0x3FFFFFFF) << 2 | flag, flag 0 ignored / 1 TP / 2 FP, ordinal =
+ * image ordinal * top_k + row; empty slots 0) and ctr, 2 c + 2 int32 words {cursor [c], npos [c], images seen, overflow}.  frost_voc_reset zeroes both.
+ * frost_voc_update: detections [n][c][k][5] rows (score, x1, y1, x2, y2; a row with score > 0 is a detection), gt [n][g][5] rows (x1, y1, x2, y2, label; class index =
+ * label < bkg_label ? label : label + 1), difficult / valid [n][g] bytes, sizes [n][2] (w, h) or NULL for 1.  Matches every detection against its image's ground truth
+ * of its class (box * size + det_offset, fp32 IoU without "+ 1", the first index of the largest IoU, IoU > ovthresh), appends its record to the class row and adds npos;
+ * then advances the images-seen word by n.  k <= top_k <= 1024, g <= 1024, max_images * top_k <= 2^30, capacity <= 2^30.  A full row or more than max_images images never writes out of
+ * bounds: the record is dropped and the overflow word set (a class cursor stops advancing at 2^30, so it cannot wrap).  Two launches on `stream`, nothing synchronises with the host.
+ * frost_voc_ap: sorted_records = the rows sorted descending as 64-bit integers -> ap [c] fp64 (the 11-point metric, or the area under the precision envelope; -1 for a
+ * class without detections, NaN for bkg_label) and counts [5][c] int64 {npos, ndet, tp, fp, ignored}. */
+int frost_voc_update(const float* detections, const float* gt, const uint8_t* difficult, const uint8_t* valid, const float* sizes, int n, int c, int k, int g,
+                     int bkg_label, float ovthresh, float det_offset, int top_k, int max_images, int64_t capacity, uint64_t* records, int32_t* ctr, void* stream);
+int frost_voc_ap(const uint64_t* sorted_records, const int32_t* ctr, int c, int64_t capacity, int bkg_label, int use_07_metric, double* ap, int64_t* counts,
+                 void* stream);
+int frost_voc_reset(uint64_t* records, int32_t* ctr, int c, int64_t capacity, void* stream);
 
 #ifdef __cplusplus
 }

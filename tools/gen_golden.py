@@ -643,6 +643,59 @@ def g15_detect():
     save("g15_detect", **out)
 
 
+# ------------------------------------------------------------------------------------------ G16 (the scoring phase)
+def g16_voc_eval():
+    """The reference's voc_eval / voc_ap (Object_Detection/qeval_convert.py:177-345) on scenes with decision margins (tests/voc_scenes.py).  Per scene the
+    reference's own input files are written into a temporary directory -- one detection file per class in write_voc_results_file's format (:123-138, the `+ 1`
+    included), the image-set file, and a pre-built annots.pkl in the cache directory so that parse_rec is never reached -- and voc_eval is called per class with
+    both metrics.  Stored: the scene's tensors, the measured margins and coverage, ap per class and metric, rec / prec per class (concatenated, with offsets)."""
+    import pickle
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import voc_scenes as V
+    voc_ap, voc_eval = refshim.load_voc_eval()
+    out = {}
+    for case, (seed0, N, C, K, G) in enumerate(((0, 6, 5, 40, 8), (100, 5, 6, 24, 5))):
+        det, gt, difficult, valid, sizes, info = V.find(seed0, N=N, C=C, K=K, G=G, offset=1.0, fill=0.25)
+        assert V.covered(info) and info["m_thresh"] >= V.M_IOU and info["m_gap"] >= V.M_IOU
+        names = [f"img{n:03d}" for n in range(N)]
+        k = f"s{case}_"
+        with tempfile.TemporaryDirectory() as tmp:
+            cache = os.path.join(tmp, "annotations_cache")
+            os.makedirs(cache)
+            with open(os.path.join(tmp, "set.txt"), "w") as f:
+                f.write("".join(name + "\n" for name in names))
+            recs = {name: [dict(name=f"c{int(gt[n, g, 4]) + 1}", difficult=int(difficult[n, g]), bbox=[float(v) for v in gt[n, g, :4]])
+                           for g in range(G) if valid[n, g]] for n, name in enumerate(names)}
+            with open(os.path.join(cache, "annots.pkl"), "wb") as f:
+                pickle.dump(recs, f)
+            for c in range(1, C):
+                with open(os.path.join(tmp, f"det_c{c}.txt"), "wt") as f:
+                    for n, name in enumerate(names):
+                        rows = det[n, c][det[n, c, :, 0] > 0]
+                        boxes = rows[:, 1:] * np.array([sizes[n, 0], sizes[n, 1], sizes[n, 0], sizes[n, 1]], dtype=np.float32)      # test_net: boxes *= w / h in fp32
+                        assert boxes.dtype == np.float32
+                        for r in range(rows.shape[0]):
+                            f.write("{:s} {:.3f} {:.1f} {:.1f} {:.1f} {:.1f}\n".format(name, rows[r, 0], boxes[r, 0] + 1, boxes[r, 1] + 1, boxes[r, 2] + 1, boxes[r, 3] + 1))
+            for metric in (1, 0):
+                aps, recl, precl, offs = np.full(C, np.nan), [], [], [0]
+                for c in range(1, C):
+                    with np.errstate(all="ignore"):
+                        rec, prec, ap = voc_eval(os.path.join(tmp, "det_{:s}.txt"), "", os.path.join(tmp, "set.txt"), f"c{c}", cache, ovthresh=0.5, use_07_metric=bool(metric))
+                    aps[c] = ap
+                    if np.ndim(rec):
+                        recl.append(np.asarray(rec, dtype=np.float64)); precl.append(np.asarray(prec, dtype=np.float64))
+                    offs.append(offs[-1] + (len(rec) if np.ndim(rec) else 0))
+                out[k + f"ap_m{metric}"] = aps
+                out[k + f"rec_m{metric}"], out[k + f"prec_m{metric}"] = np.concatenate(recl), np.concatenate(precl)
+                out[k + "curve_offsets"] = np.array(offs)
+        out[k + "det"], out[k + "gt"], out[k + "difficult"], out[k + "valid"], out[k + "sizes"] = det, gt, difficult, valid, sizes
+        out[k + "margins"] = np.array([info["m_thresh"], info["m_gap"]])
+        out[k + "coverage"] = np.array([info[q] for q in ("tp", "dup", "near", "difficult_twice", "partial_class", "gt_only", "det_only", "image_without_gt", "sizes", "redrawn", "rows")])
+        print(f"  g16 scene {case}: seed {info['seed']}, margins {out[k + 'margins']}, coverage {out[k + 'coverage'].tolist()}, ap07 {out[k + 'ap_m1']}, ap area {out[k + 'ap_m0']}")
+    save("g16_voc_eval", **out)
+
+
 # ------------------------------------------------------------------------------------------ G12 (SURVEY N4 / Appendix E)
 def g12_fbgemm():
     """Per-channel mode = the reference's 'fbgemm' qconfig (Classification/latency_check.py:221-226), QAT flavour, version 0: activations quint8
@@ -716,8 +769,8 @@ def g8_features():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g3c", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g4t"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g3c", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g4t"]
     fns = dict(g1=g1_fake_quant, g2=g2_observer, g3=g3_layers, g3c=g3_classifier, g4=g4_blocks, g5=g5_wholenet, g6=g6_optimizers,
-               g7=g7_scalars, g8=g8_features, g9=g9_convert, g10=g10_hswish, g11=g11_detection, g12=g12_fbgemm, g13=g13_convert_fbgemm, g14=g14_hswish_converted, g15=g15_detect, g4t=g4_true_shapes)
+               g7=g7_scalars, g8=g8_features, g9=g9_convert, g10=g10_hswish, g11=g11_detection, g12=g12_fbgemm, g13=g13_convert_fbgemm, g14=g14_hswish_converted, g15=g15_detect, g16=g16_voc_eval, g4t=g4_true_shapes)
     for w in which:
         fns[w]()

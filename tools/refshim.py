@@ -128,6 +128,24 @@ def load_detect_layer(min_dim, variance):
     return det.Detect
 
 
+def load_voc_eval():
+    """The reference's `voc_ap` and `voc_eval` (Object_Detection/qeval_convert.py).  The file is a script that imports cv2-dependent modules and never imports the
+    `ET` it uses, so it cannot be imported: it is parsed in place, the two function definitions alone are compiled and executed in a namespace that holds numpy
+    (with the `np.bool` alias that numpy >= 1.24 dropped), os and pickle.  Nothing is copied or written."""
+    import ast
+    import pickle
+    import numpy as np
+    path = f"{REF}/Object_Detection/qeval_convert.py"
+    tree = ast.parse(open(path).read(), filename=path)
+    tree.body = [node for node in tree.body if isinstance(node, ast.FunctionDef) and node.name in ("voc_ap", "voc_eval")]
+    assert [node.name for node in tree.body] == ["voc_ap", "voc_eval"]
+    if not hasattr(np, "bool"):
+        np.bool = bool
+    ns = dict(np=np, os=os, pickle=pickle)
+    exec(compile(tree, path, "exec"), ns)
+    return ns["voc_ap"], ns["voc_eval"]
+
+
 def load_optimizer():
     if "ref_optimizer" in sys.modules:
         return sys.modules["ref_optimizer"]
