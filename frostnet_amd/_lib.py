@@ -108,6 +108,9 @@ _PROTOS = {
     "frost_voc_update": [P, P, P, P, P, I, I, I, I, I, F, F, I, I, L, P, P, P],
     "frost_voc_ap": [P, P, I, L, I, I, P, P, P],
     "frost_voc_reset": [P, P, I, L, P],
+    "frost_aug_plan_words": [],
+    "frost_aug_plan": [P, P, P, I, I, P, P, P, P, P],
+    "frost_aug_apply": [P, P, P, I, I, I, I, F, F, F, I, P, P],
     "frost_stats_init_table": [P, P, P, I, P],
     "frost_pw_conv_fwd": [P, P, P, P, L, I, I, I, P, P, P, I, P, P],
     "frost_pw_conv_fwd_fin": [P, P, P, P, L, I, I, P, P, P],

@@ -42,7 +42,8 @@ extern "C" {
  *          New entries (additive): frost_step_prologue, frost_block_dw_bwd_c1 / _c1_ok, frost_hswish_converted.  The `relu` argument of the frost_float_* and
  *          frost_infer_pw / _dw / _stem entries is an activation code: 0 none, 1 ReLU, 2 hard-swish (0 / 1 mean what they meant).
  *          New entries (additive): frost_float_ssd_gather[_f32] / frost_float_ssd_scatter[_f32] with the FrostSSDMap table (the float SSDLite detector).
- *          New entries (additive): frost_voc_update / frost_voc_ap / frost_voc_reset (the PASCAL VOC mean-AP evaluator). */
+ *          New entries (additive): frost_voc_update / frost_voc_ap / frost_voc_reset (the PASCAL VOC mean-AP evaluator).
+ *          New entries (additive): frost_aug_plan / frost_aug_apply / frost_aug_plan_words (SSD training-time augmentation, the FROST_AUG_* plan record). */
 #ifndef FROST_DWQ_NC          /* (a -D override is a dev A/B build: the binding must be told the same value, FROST_DWQ_NC / FROST_COEF_ROWS_ALLOC / FROST_STATS_TABLES in the environment) */
 #define FROST_DWQ_NC 4
 #endif
@@ -733,6 +734,61 @@ int frost_voc_update(const float* detections, const float* gt, const uint8_t* di
 int frost_voc_ap(const uint64_t* sorted_records, const int32_t* ctr, int c, int64_t capacity, int bkg_label, int use_07_metric, double* ap, int64_t* counts,
                  void* stream);
 int frost_voc_reset(uint64_t* records, int32_t* ctr, int c, int64_t capacity, void* stream);
+
+/* ---- SSD training-time augmentation (Object_Detection/utils/augmentations.py:400-417 SSDAugmentation, data/__init__.py:30-43 BaseTransform) ------------------------
+ * Two halves.  frost_aug_plan takes every random decision of the reference's pipeline, in its order, and writes one record per image plus the transformed targets;
+ * frost_aug_apply is a pure function of (images, sizes, plan).  The definition both follow, fp32 operation by operation, is frostnet_amd/augment.py on CPU tensors.
+ * The plan record: FROST_AUG_PLAN_WORDS 32-bit words per image, [n][FROST_AUG_PLAN_WORDS]; (f) = fp32 bits, (i) = int32.  Unused factors hold their neutral values, so
+ * the pixel kernel does not branch on coins.  W, H = the canvas: the image, or after Expand int(h * ratio) x int(w * ratio). */
+#define FROST_AUG_PLAN_WORDS 24
+#define FROST_AUG_FLAGS 0       /* (i) FROST_AUG_F_* bits: the coins as drawn, and whether the BGR -> HSV -> BGR round trip runs */
+#define FROST_AUG_DELTA 1       /* (f) RandomBrightness: added to every channel; 0 */
+#define FROST_AUG_ALPHA_PRE 2   /* (f) RandomContrast when it runs before the HSV round trip; 1 */
+#define FROST_AUG_ALPHA_POST 3  /* (f) RandomContrast when it runs after it; 1 */
+#define FROST_AUG_SAT 4         /* (f) RandomSaturation: factor on S; 1 */
+#define FROST_AUG_HUE 5         /* (f) RandomHue: degrees added to H, then `> 360 -> - 360`, `< 0 -> + 360`; 0 */
+#define FROST_AUG_PERM 6        /* (i) RandomLightingNoise: index into ((0,1,2), (0,2,1), (1,0,2), (1,2,0), (2,0,1), (2,1,0)), out[c] = in[perm[c]]; 0 */
+#define FROST_AUG_RATIO 7       /* (f) Expand: the drawn ratio; 1 (kept for inspection, the kernels read the integer words below) */
+#define FROST_AUG_PASTE_X 8     /* (i) Expand: int(left), the image's column on the canvas; 0 */
+#define FROST_AUG_PASTE_Y 9     /* (i) Expand: int(top); 0 */
+#define FROST_AUG_CANVAS_W 10   /* (i) W */
+#define FROST_AUG_CANVAS_H 11   /* (i) H */
+#define FROST_AUG_MODE 12       /* (i) RandomSampleCrop: the sample option 0 .. 5 that ended the loop; 0 = the whole canvas, no centre test, no clipping of boxes */
+#define FROST_AUG_ROUNDS 13     /* (i) mode draws used, 0 .. FROST_AUG_MAX_ROUNDS (0: the image had no valid box) */
+#define FROST_AUG_X1 14         /* (i) the crop rect (int(left), int(top), int(left + w), int(top + h)), UNCLIPPED: x2 / y2 may exceed W / H by one.  Pixels come from */
+#define FROST_AUG_Y1 15         /*     the rect clipped to the canvas, boxes are clipped to the unclipped rect, percent coordinates and the mirror use the clipped extent */
+#define FROST_AUG_X2 16
+#define FROST_AUG_Y2 17
+#define FROST_AUG_DRAWN_W 18    /* (f) the accepted trial's w and h as drawn (0.3 W <= w <= W, 0.5 <= h / w <= 2); 0 in mode 0 */
+#define FROST_AUG_DRAWN_H 19
+/* words 20 .. 23: zero */
+#define FROST_AUG_F_BRIGHT 1
+#define FROST_AUG_F_CONTRAST_FIRST 2   /* PhotometricDistort's randint(2): contrast before the HSV round trip */
+#define FROST_AUG_F_CONTRAST 4
+#define FROST_AUG_F_SAT 8
+#define FROST_AUG_F_HUE 16
+#define FROST_AUG_F_NOISE 32
+#define FROST_AUG_F_EXPAND 64          /* the image was expanded (the reference's randint(2) came up 0) */
+#define FROST_AUG_F_MIRROR 128         /* read by frost_aug_apply */
+#define FROST_AUG_F_HSV 256            /* read by frost_aug_apply: the round trip runs.  Set by every drawn plan (the reference always converts), clear in an identity plan */
+#define FROST_AUG_MAX_ROUNDS 64        /* bound of RandomSampleCrop's outer `while True` (this library's definition): then mode 0 */
+#define FROST_AUG_TRIALS 50
+#define FROST_AUG_MAX_G 1024
+#define FROST_AUG_MAX_SIZE 4096
+/* frost_aug_plan: sizes [n][2] int32 (h, w), boxes [n][g][5] rows (x1, y1, x2, y2 as fractions of the image, label), valid [n][g] bytes; state: int64 {seed, images seen}
+ * in device memory.  Philox4x32-10, key = seed, counter = (image ordinal low, high, draw block, 0x53534441), image ordinal = images seen + index in the batch; draw k is
+ * word k & 3 of block k >> 2; u = (word >> 8) * 2^-24, coin = top bit, choice among k = high 32 bits of word * k, uniform(a, b) = a + (b - a) * u.  Writes plan,
+ * boxes_out [n][g][5] and valid_out [n][g] (survivors keep their rows; a dropped row is zeros), then a one-thread launch adds n to the images-seen word.
+ * 1 <= n <= 65535, 1 <= g <= FROST_AUG_MAX_G.  Every sizes row is TRUSTED to be >= 1.
+ * frost_aug_apply: images [n][hmax][wmax][3] uint8 BGR, each image in the top-left corner of its slot -> x fp32 [n][3][size][size], or [n][size][size][3] when
+ * channels_last.  Per output pixel: OpenCV INTER_LINEAR taps over the clipped crop, mirrored, offset into the canvas; inside the pasted image the source pixel through
+ * the photometric chain, outside it `mean` undistorted; horizontal then vertical lerp; minus mean.  1 <= size <= FROST_AUG_MAX_SIZE, hmax, wmax >= 1; every sizes
+ * row is TRUSTED to lie in [1, hmax] x [1, wmax]; any plan contents are memory-safe.  Nothing synchronises with the host. */
+int frost_aug_plan_words(void);
+int frost_aug_plan(const int32_t* sizes, const float* boxes, const uint8_t* valid, int n, int g, int64_t* state, int32_t* plan, float* boxes_out, uint8_t* valid_out,
+                   void* stream);
+int frost_aug_apply(const uint8_t* images, const int32_t* sizes, const int32_t* plan, int n, int hmax, int wmax, int size, float mean_b, float mean_g, float mean_r,
+                    int channels_last, float* x, void* stream);
 
 #ifdef __cplusplus
 }
