@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FROST_HIP_LIB", os.path.join(_HERE, "libfrost_hip.so"))   # override: A/B runs of two builds in one GPU session (dev only)
 _lib = None
 
-P, I, L, F = C.c_void_p, C.c_int, C.c_int64, C.c_float
+P, I, L, F, D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 Q_MIN, Q_MAX, Q_SCALE, Q_ZP, Q_FQMIN, Q_FQMAX, Q_INV, Q_QMAX, Q_OBS_EN, Q_FQ_EN, Q_STRIDE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12
 COEF_ROWS = int(os.environ.get("FROST_COEF_ROWS_ALLOC", "14"))          # FROST_COEF_ROWS_ALLOC: the 8 named rows + three more copies of the S1 / S2 rows (ABI 5: the reduce passes spread their atomics, readers add the copies up)
@@ -111,6 +111,10 @@ _PROTOS = {
     "frost_aug_plan_words": [],
     "frost_aug_plan": [P, P, P, I, I, P, P, P, P, P],
     "frost_aug_apply": [P, P, P, I, I, I, I, F, F, F, I, P, P],
+    "frost_caug_plan_words": [],
+    "frost_caug_plan": [P, I, I, D, D, D, D, D, D, P, P, P],
+    "frost_caug_eval_plan": [P, I, I, I, P, P],
+    "frost_caug_apply": [P, P, P, I, I, I, I, F, F, F, F, F, F, I, P, P],
     "frost_stats_init_table": [P, P, P, I, P],
     "frost_pw_conv_fwd": [P, P, P, P, L, I, I, I, P, P, P, I, P, P],
     "frost_pw_conv_fwd_fin": [P, P, P, P, L, I, I, P, P, P],

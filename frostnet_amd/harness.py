@@ -118,11 +118,17 @@ def _device_of(model):
     return next(model.parameters()).device
 
 
-def _epoch(loader, model, criterion, optimizer, epoch, args, grad_sync, train_mode):
+def _epoch(loader, model, criterion, optimizer, epoch, args, grad_sync, train_mode, transform=None):
     dev = _device_of(model)
     sums, n = torch.zeros(3, dtype=torch.float64, device=dev), 0
-    for i, (inp, target) in enumerate(loader):
-        inp, target = inp.to(dev, non_blocking=True), target.to(dev, non_blocking=True)
+    for i, batch in enumerate(loader):
+        if transform is None:
+            inp, target = batch
+            inp = inp.to(dev, non_blocking=True)
+        else:                                    # (images uint8 [N, Hmax, Wmax, 3], sizes int32 [N, 2], target): the transform runs on the device, in front of the model
+            images, sizes, target = batch
+            inp = transform(images.to(dev, non_blocking=True), sizes.to(dev, non_blocking=True))
+        target = target.to(dev, non_blocking=True)
         if train_mode:
             if args is not None and getattr(args, "lrsch", "cos_lr") == "cos_lr" and hasattr(args, "dataset_len"):
                 adjust_learning_rate_cosine(optimizer, epoch, i, args.dataset_len, args)
@@ -140,17 +146,18 @@ def _epoch(loader, model, criterion, optimizer, epoch, args, grad_sync, train_mo
     return loss, a1, a5
 
 
-def train(train_loader, model, criterion, optimizer, epoch, total_ep=None, args=None, grad_sync=None):
-    """One training epoch (helper_functions.py:99-163): returns (mean loss, mean top-1, mean top-5) over the iterations."""
+def train(train_loader, model, criterion, optimizer, epoch, total_ep=None, args=None, grad_sync=None, transform=None):
+    """One training epoch (helper_functions.py:99-163): returns (mean loss, mean top-1, mean top-5) over the iterations.  With a `transform` (a
+    `ClassificationAugmentation`) the loader yields (images uint8, sizes, target) in `pad_images`' format and the transform turns them into the model's input on the device."""
     model.train()
-    return _epoch(train_loader, model, criterion, optimizer, epoch, args, grad_sync, True)
+    return _epoch(train_loader, model, criterion, optimizer, epoch, args, grad_sync, True, transform)
 
 
-def val(val_loader, model, criterion):
+def val(val_loader, model, criterion, transform=None):
     """One validation pass (helper_functions.py:306-350): `model.eval()` only -- BatchNorm uses its running statistics while every FakeQuantize
-    observer that has not been disabled explicitly keeps updating, exactly as the reference's val() leaves them."""
+    observer that has not been disabled explicitly keeps updating, exactly as the reference's val() leaves them.  `transform` (a `ClassificationEvalTransform`): as in `train`."""
     model.eval()
-    return _epoch(val_loader, model, criterion, None, 0, None, None, False)
+    return _epoch(val_loader, model, criterion, None, 0, None, None, False, transform)
 
 
 def val_detector(loader, model, evaluator, top_k=200, conf_thresh=0.01, nms_thresh=0.45):

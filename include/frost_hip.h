@@ -43,7 +43,8 @@ extern "C" {
  *          frost_infer_pw / _dw / _stem entries is an activation code: 0 none, 1 ReLU, 2 hard-swish (0 / 1 mean what they meant).
  *          New entries (additive): frost_float_ssd_gather[_f32] / frost_float_ssd_scatter[_f32] with the FrostSSDMap table (the float SSDLite detector).
  *          New entries (additive): frost_voc_update / frost_voc_ap / frost_voc_reset (the PASCAL VOC mean-AP evaluator).
- *          New entries (additive): frost_aug_plan / frost_aug_apply / frost_aug_plan_words (SSD training-time augmentation, the FROST_AUG_* plan record). */
+ *          New entries (additive): frost_aug_plan / frost_aug_apply / frost_aug_plan_words (SSD training-time augmentation, the FROST_AUG_* plan record).
+ *          New entries (additive): frost_caug_plan / frost_caug_eval_plan / frost_caug_apply / frost_caug_plan_words (the classifier's input pipeline, FROST_CAUG_*). */
 #ifndef FROST_DWQ_NC          /* (a -D override is a dev A/B build: the binding must be told the same value, FROST_DWQ_NC / FROST_COEF_ROWS_ALLOC / FROST_STATS_TABLES in the environment) */
 #define FROST_DWQ_NC 4
 #endif
@@ -789,6 +790,46 @@ int frost_aug_plan(const int32_t* sizes, const float* boxes, const uint8_t* vali
                    void* stream);
 int frost_aug_apply(const uint8_t* images, const int32_t* sizes, const int32_t* plan, int n, int hmax, int wmax, int size, float mean_b, float mean_g, float mean_r,
                     int channels_last, float* x, void* stream);
+
+/* ---- the classifier's input pipeline (Classification/utils/data_functions.py:23-42: RandomResizedCrop -> RandomHorizontalFlip -> ToTensor -> Normalize for training,
+ * Resize -> CenterCrop -> ToTensor -> Normalize for validation) -----------------------------------------------------------------------------------------------------
+ * Two halves, as above.  A plan record says which rect of the source is resized to which grid, and where the size x size output window lies in that grid;
+ * frost_caug_apply is a pure function of (images, sizes, plan).  The definition all entries follow is frostnet_amd/cls_augment.py on CPU tensors: fp64 decisions with
+ * exp as a written-out degree-13 Horner polynomial, and Pillow's antialiased two-pass triangle resampler (fp64 weights, 22-bit fixed-point coefficients, uint8
+ * intermediate).  The plan record: FROST_CAUG_PLAN_WORDS int32 words per image, [n][FROST_CAUG_PLAN_WORDS]. */
+#define FROST_CAUG_PLAN_WORDS 12
+#define FROST_CAUG_FLAGS 0      /* FROST_CAUG_F_* bits */
+#define FROST_CAUG_X0 1         /* the crop rect in the source image: left, top, width, height */
+#define FROST_CAUG_Y0 2
+#define FROST_CAUG_W 3
+#define FROST_CAUG_H 4
+#define FROST_CAUG_RW 5         /* the grid the crop is resized to (training: size x size) */
+#define FROST_CAUG_RH 6
+#define FROST_CAUG_OX 7         /* the output is the size x size window of the grid that starts here (training: 0, 0) */
+#define FROST_CAUG_OY 8
+#define FROST_CAUG_TRIES 9      /* trials of RandomResizedCrop.get_params used, 1 .. FROST_CAUG_TRIALS; 0 in a validation record */
+/* words 10, 11: zero */
+#define FROST_CAUG_F_MIRROR 1          /* read by frost_caug_apply: out[x] = window[size - 1 - x] */
+#define FROST_CAUG_F_FALLBACK 2        /* every trial failed: the central crop of torchvision's fallback */
+#define FROST_CAUG_TRIALS 10
+#define FROST_CAUG_MAX_TAPS 9          /* the cap of frost_caug_apply's LDS path: 2 * ceil(crop side / grid side) + 1 taps per axis, i.e. ceil(scale) <= 4 (a 896-pixel
+                                          crop at 224); a crop beyond it takes the kernel's general path (same result, coefficients recomputed per tap) */
+/* frost_caug_plan: sizes [n][2] int32 (h, w); state: int64 {seed, images seen} in device memory.  Philox4x32-10 with frost_aug_plan's conventions and the counter
+ * word 0x43524F50.  Per trial, in fp64: target = h w (scale_lo + (scale_hi - scale_lo) u), aspect = exp_poly(log_ratio_lo + (log_ratio_hi - log_ratio_lo) u'),
+ * w = rint(sqrt(target * aspect)), h = rint(sqrt(target / aspect)); accepted iff 0 < w <= w0 and 0 < h <= h0, then Y0 = choice(h0 - h + 1), X0 = choice(w0 - w + 1).
+ * After FROST_CAUG_TRIALS failures the central fallback; then one coin for the mirror.  Writes plan, then a one-thread launch adds n to the images-seen word.
+ * 1 <= n <= 65535, 1/2 <= ratio_lo <= ratio_hi <= 2, 0 < scale_lo <= scale_hi.  Every sizes row is TRUSTED to be >= 1.
+ * frost_caug_eval_plan: Resize(resize) + CenterCrop(size) as plan records: the whole image, the shorter side -> resize and the longer -> resize * long / short
+ * (integer division), the window at round-half-even((grid - size) / 2).  1 <= size <= resize <= FROST_AUG_MAX_SIZE.
+ * frost_caug_apply: images [n][hmax][wmax][3] uint8, each image in the top-left corner of its slot -> x fp32 [n][3][size][size], or [n][size][size][3] when
+ * channels_last; x[c] = ((v / 255) - mean_c) / std_c of the resized window's byte v, each operation rounded to fp32.  1 <= size <= FROST_AUG_MAX_SIZE; every sizes
+ * row is TRUSTED to lie in [1, hmax] x [1, wmax]; any plan contents are memory-safe (rect and grid are clamped into the slot).  Nothing synchronises with the host. */
+int frost_caug_plan_words(void);
+int frost_caug_plan(const int32_t* sizes, int n, int size, double scale_lo, double scale_hi, double log_ratio_lo, double log_ratio_hi, double ratio_lo, double ratio_hi,
+                    int64_t* state, int32_t* plan, void* stream);
+int frost_caug_eval_plan(const int32_t* sizes, int n, int size, int resize, int32_t* plan, void* stream);
+int frost_caug_apply(const uint8_t* images, const int32_t* sizes, const int32_t* plan, int n, int hmax, int wmax, int size, float mean0, float mean1, float mean2,
+                     float std0, float std1, float std2, int channels_last, float* x, void* stream);
 
 #ifdef __cplusplus
 }
