@@ -1,6 +1,6 @@
 """One seeded forward + backward of a bottleneck's conv1 -> conv2 -> reduce_conv chain (Engine.conv_pair + Engine.conv, Engine.backward); dumps every result.
 Used by tests/test_gpu_block.py to hold the block-level kernels (environment switches read at import / library load, hence one subprocess per
-configuration) to the layer-by-layer launches.   usage: block_digest.py out.npz cin cexp H k cout B [stride of conv2 = 1]"""
+configuration) to the layer-by-layer launches.   usage: block_digest.py out.npz cin cexp H k cout B [stride of conv2 = 1]      (DIGEST_PER_CHANNEL=1: all three layers in per-channel + reduce_range mode)"""
 import os, sys, warnings
 warnings.filterwarnings("ignore")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,6 +27,12 @@ def layer(name, kind, ci, co, kk, relu, stride=1):
 
 
 l1, l2, l3 = layer("conv1", "pw", cin, cexp, 1, True), layer("conv2", "dw", cexp, cexp, k, True, stride2), layer("reduce", "pw", cexp, cout, 1, False)
+if os.environ.get("DIGEST_PER_CHANNEL") == "1":          # the 'fbgemm' qconfig: per-channel weight observer / scales, reduce_range activations (indices 0..127)
+    for l in (l1, l2, l3):
+        l.per_channel = True
+        l.wmin, l.wmax = torch.full((l.cout,), float("inf"), device=dev), torch.full((l.cout,), float("-inf"), device=dev)
+    qa.t[:, L.Q_QMAX] = 127.0
+    E.act_qmax = 127
 qx = qa.alloc(); qa.set_qparams(qx, 0.02, 3)
 x = E.new_act(B, H, H, cin, qx)
 x.buf[: x.numel] = torch.randint(-128, 128, (x.numel,), dtype=torch.int16, generator=g).to(torch.int8).to(dev)

@@ -1,7 +1,7 @@
 """One seeded forward + backward of a single conv layer through the engine; dumps every result to an .npz.
 Used by tests/test_gpu_paths.py to hold the fast kernel paths (resident weights, DMA / LDS-staged tile I/O, channel split,
 depthwise tile geometries, fused passes -- all selected by size) to the plain paths at sizes where they actually engage.
-usage: layer_digest.py out.npz kind cin cout k stride H B"""
+usage: layer_digest.py out.npz kind cin cout k stride H B      (DIGEST_PER_CHANNEL=1: the layer in per-channel + reduce_range mode)"""
 import os, sys, warnings
 warnings.filterwarnings("ignore")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,6 +22,11 @@ beta = (torch.rand(cout, generator=g) * 0.2 - 0.05).to(dev).requires_grad_(True)
 rm, rv = torch.zeros(cout, device=dev), torch.ones(cout, device=dev)
 relu = os.environ.get("DIGEST_RELU", "1") == "1"
 l = EN.ConvLayer("L", kind, w, gamma, beta, rm, rv, torch.zeros((), dtype=torch.int64, device=dev), None, k, stride, relu, qa.alloc(), qa.alloc())
+if os.environ.get("DIGEST_PER_CHANNEL") == "1":          # the 'fbgemm' qconfig: per-channel weight observer / scales, reduce_range activations (indices 0..127)
+    l.per_channel = True
+    l.wmin, l.wmax = torch.full((cout,), float("inf"), device=dev), torch.full((cout,), float("-inf"), device=dev)
+    qa.t[:, L.Q_QMAX] = 127.0
+    E.act_qmax = 127
 E.add_layer(l)
 qx = qa.alloc(); qa.set_qparams(qx, 0.02, 3)
 x = E.new_act(B, H, H, cin, qx)
