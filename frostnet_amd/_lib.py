@@ -44,6 +44,12 @@ class FrostSSDMap(C.Structure):
                 ("cpad", C.c_int32), ("which", C.c_int32)]
 
 
+class FrostCvtHead(C.Structure):
+    """One SepHead of the converted detector, named by its layers' device arrays (a HOST struct, include/frost_hip.h)."""
+    _fields_ = [("dw_wq", P), ("dw_wsum", P), ("dw_coef", P), ("dw_qy", P), ("pw_wq", P), ("pw_wsum", P), ("pw_coef", P), ("pw_qy", P),
+                ("cout", C.c_int32), ("reserved", C.c_int32)]
+
+
 ABI_VERSION = 5
 TICKET_WORDS = 40      # FROST_TICKET_WORDS: zeroed uint32 words behind every last-workgroup-done ticket (main counter + 32 sub-counters)
 
@@ -249,6 +255,9 @@ _PROTOS = {
     "frost_conv_finalize_converted_fb": [P, P, P, P, P, P, I, P, P, P],
     "frost_add_qnnpack": [P, P, P, P, L, P, P, P],
     "frost_avgpool_q": [P, I, I, I, P, P],
+    "frost_cvt_head_ok": [I, I, I, I, I],
+    "frost_cvt_head": [P, P, P, P, I, I, I, I, I, I, I, P, L, L, P, L, L, P],
+    "frost_cvt_place": [P, P, I, I, I, I, P, L, L, P],
     "frost_stem_converted_ok": [I],
     "frost_stem_converted": [P, I, I, I, L, L, L, L, P, P, P, P, P, I, I, P, P],
     "frost_hswish_fwd": [P, P, L, P, P, P, P, I, P, P, P],

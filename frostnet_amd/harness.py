@@ -163,18 +163,21 @@ def val(val_loader, model, criterion, transform=None):
 def val_detector(loader, model, evaluator, top_k=200, conf_thresh=0.01, nms_thresh=0.45):
     """One validation pass of the detector: `model.eval()`, then for every (images, gt [N, G, 5], difficult [N, G], valid [N, G], sizes [N, 2] or None) of the
     loader (ssdlite.pad_targets / voc_eval.pad_difficult turn ragged targets into these) the detections [N, C, top_k, 5] go into `evaluator.update` -- from
-    `model.hip_detect_bf16` when the model is the float detector on the device, from `model.detect` otherwise.  Returns (mean AP, per-class AP list) after the
+    `model.hip_detect_bf16` when the model is the float detector on the device, from `model.hip_detect_int8` when it is the hip_convert()-ed detector on the
+    device, from `model.detect` otherwise.  Returns (mean AP, per-class AP list) after the
     evaluation's single read of the results; the evaluator is reset first and keeps the evaluation's state (counts, records) afterwards."""
     model.eval()
     dev = _device_of(model)
     is_qat = getattr(model, "_is_qat_prepared", None)
     bf16 = dev.type == "cuda" and hasattr(model, "hip_detect_bf16") and not (is_qat() if is_qat is not None else False) \
         and not getattr(model, "_hip_converted", False)
+    int8 = dev.type == "cuda" and hasattr(model, "hip_detect_int8") and bool(getattr(model, "_hip_converted", False))      # (bit-equal to model.detect)
+    detect = model.hip_detect_bf16 if bf16 else (model.hip_detect_int8 if int8 else model.detect)
     evaluator.reset()
     n = 0
     for images, gt, difficult, valid, sizes in loader:
         x = images.to(dev, non_blocking=True)
-        det = model.hip_detect_bf16(x, top_k, conf_thresh, nms_thresh) if bf16 else model.detect(x, top_k, conf_thresh, nms_thresh)
+        det = detect(x, top_k, conf_thresh, nms_thresh)
         evaluator.update(det, gt.to(dev, non_blocking=True), difficult.to(dev, non_blocking=True), valid.to(dev, non_blocking=True),
                          None if sizes is None else sizes.to(dev, non_blocking=True))
         n += 1

@@ -349,6 +349,16 @@ def ssd_head_offsets(anchors, map_sizes):
     return offs
 
 
+def cvt_place_torch(idx, scale, zero_point, width, out, off):
+    """The definition of frost_cvt_place (and of the store of frost_cvt_head) as torch stages on any device: idx [n, hw, cout] int8 offset-binary indices (index - 128)
+    of one head map under (scale, zero_point); the first `width` channels of every pixel, dequantised as (float)(index - zero_point) * scale in fp32, go to
+    out[:, off : off + hw * width] of the image rows out [n, stride]; nothing else of `out` is written."""
+    n, hw, _ = idx.shape
+    v = (idx.to(torch.int32) + 128 - int(zero_point)).to(torch.float32) * torch.tensor(float(scale), dtype=torch.float32, device=idx.device)
+    out[:, off:off + hw * width] = v[:, :, :width].reshape(n, -1)
+    return out
+
+
 class Bf16SSDInference(Bf16Inference):
     """Binds a float SSDLiteFrostNet (eval mode) to the bf16 HIP inference kernels.  `__call__(x)` -> (loc [N,P,4], conf [N,P,C]) fp32 in _assemble's order:
     the trunk on the fused bottleneck kernels with taps at the ends of stages 1, 2 and 4 (0-based), every extra stage as frost_infer_pw -> frost_infer_dw

@@ -7,6 +7,7 @@ those scalars on-device.  Parameter gradients live in ONE flat fp32 arena (views
 the multi-tensor optimizer and the data-parallel all-reduce operate on.
 """
 import os
+from ctypes import byref as C_byref
 
 import torch
 
@@ -15,6 +16,10 @@ from .engine import ConvLayer, Engine, QArena
 
 
 _STEM_COL_EARLY = os.environ.get("FROST_STEM_COL_EARLY", "1") != "0"      # the stem's im2col in front of the join with the weight-preparation stream (A/B)
+# prediction heads of the converted detector (SSDRunner.infer_converted): "1" = both heads of every source in ONE launch (csrc/frost_iheadq.hip), "0" = layer launches +
+# frost_cvt_place, "auto" (default) = per source what measured faster (profiles/detect_int8_b32_512.txt): the sources listed in _CVT_HEAD_LAYERWISE run layer-wise
+_CVT_HEAD = os.environ.get("FROST_CVT_HEAD", "auto")
+_CVT_HEAD_LAYERWISE = frozenset({0})      # the stride-8 source (64 x 64 x 40 at 512 x 512): 0.058 ms as layer launches against 0.074 ms fused at B = 32
 _PREP_SIDE = os.environ.get("FROST_PREP_SIDE", "1") != "0"      # training: the per-step weight preparation on a second stream beside the QuantStub passes
 
 class _QATFunction(torch.autograd.Function):
@@ -682,9 +687,8 @@ class SSDRunner(FrostRunner):
             self.heads.append((self._conv_layer(f"loc.{i}.dw", l.dw, "dw"), self._conv_layer(f"loc.{i}.pw", l.pw, "pw"),
                                self._conv_layer(f"conf.{i}.dw", c.dw, "dw"), self._conv_layer(f"conf.{i}.pw", c.pw, "pw")))
 
-    def _maps_converted(self, x):
-        """The converted detector (Object_Detection/qeval_convert.py: torch.quantization.convert of the QAT SSD): backbone, extras and the separable
-        prediction heads as quantized convs with the requantisation epilogue; twelve maps."""
+    def _sources_converted(self, x):
+        """The six source activations of the converted detector: stage ends 1, 2 and 4 (0-based) of the trunk, then the output of every extra stage."""
         E, fb = self.E, getattr(self, "converted_fb", False)
         a, feats = self._trunk_converted(x)
         ends = self._stage_ends(feats)
@@ -692,12 +696,73 @@ class SSDRunner(FrostRunner):
         for pw1, dw, pw2 in self.extras:
             a = E.conv_converted(pw2, E.conv_converted(dw, E.conv_converted(pw1, a, fb), fb), fb)
             sources.append(a)
+        return sources
+
+    def _maps_converted(self, x):
+        """The converted detector (Object_Detection/qeval_convert.py: torch.quantization.convert of the QAT SSD): backbone, extras and the separable
+        prediction heads as quantized convs with the requantisation epilogue; twelve maps."""
+        E, fb = self.E, getattr(self, "converted_fb", False)
+        sources = self._sources_converted(x)
         maps = []
         for s, (ldw, lpw, cdw, cpw) in zip(sources, self.heads):
             maps.append(E.conv_converted(lpw, E.conv_converted(ldw, s, fb), fb))
             maps.append(E.conv_converted(cpw, E.conv_converted(cdw, s, fb), fb))
         E.tape = []
         return maps
+
+    def _cvt_head_fused(self, k, s, lpw, cpw):
+        """Whether source k's heads run as ONE frost_cvt_head launch: the geometry must be taken, then FROST_CVT_HEAD decides ("1" / "0": every source fused /
+        as layer launches + frost_cvt_place; "auto": per source, what profiles/detect_int8_b32_512.txt measured faster)."""
+        if _CVT_HEAD == "0" or not L.load_library().frost_cvt_head_ok(s.h, s.w, s.c, lpw.cout, cpw.cout):
+            return False
+        return True if _CVT_HEAD == "1" else k not in _CVT_HEAD_LAYERWISE
+
+    def _head_converted(self, k, s, layers, loc, conf, poff, p):
+        """Both SepHeads of source k into their region of the image rows of loc [N,P,4] / conf [N,P,C] (infer.ssd_head_offsets)."""
+        E, fb = self.E, getattr(self, "converted_fb", False)
+        ldw, lpw, cdw, cpw = layers
+        A, C = self.model.ANCHORS[k], self.model.num_classes
+        if self._cvt_head_fused(k, s, lpw, cpw):
+            descs = []
+            for dw, pw in ((ldw, lpw), (cdw, cpw)):
+                E._converted_coef(dw, s.q, fb)           # cached per (layer, input record): launches only on the first call
+                E._converted_coef(pw, dw.qy, fb)
+                d = L.FrostCvtHead()
+                d.dw_wq, d.dw_wsum, d.dw_coef, d.dw_qy = dw.wq_pack.data_ptr(), dw.wsum.data_ptr(), dw.coef.data_ptr(), dw.qy.data_ptr()
+                d.pw_wq, d.pw_wsum, d.pw_coef, d.pw_qy = pw.wq_pack.data_ptr(), pw.wsum.data_ptr(), pw.coef.data_ptr(), pw.qy.data_ptr()
+                d.cout = pw.cout
+                descs.append(d)
+            L.call("frost_cvt_head", L.ptr(s.buf), L.ptr(s.q), C_byref(descs[0]), C_byref(descs[1]), s.n, s.h, s.w, s.c, 4 * A, C * A, 3 if fb else 2,
+                   L.ptr(loc), p * 4, poff * 4, L.ptr(conf), p * C, poff * C, L.stream())
+            return
+        # layer launches + one placement per map (geometries the fused kernel does not take; FROST_CVT_HEAD=0)
+        for dw, pw, out, unit in ((ldw, lpw, loc, 4), (cdw, cpw, conf, C)):
+            y = E.conv_converted(pw, E.conv_converted(dw, s, fb), fb)
+            L.call("frost_cvt_place", L.ptr(y.buf), L.ptr(y.q), y.n, y.h * y.w, y.c, A * unit, L.ptr(out), p * unit, poff * unit, L.stream())
+
+    def infer_converted(self, x):
+        """The converted detector's inference path -> (loc [N,P,4], conf [N,P,C]) fp32 in SSDLiteFrostNet._assemble's order, bit-equal to
+        _assemble(forward_maps(x)): trunk and extras as in forward_maps, then per source either one launch that computes both heads and stores the dequantised values
+        straight into loc / conf (frost_cvt_head: no int8 head map) or the four layer launches + two frost_cvt_place (see _cvt_head_fused) -- no NCHW copy, no cat.  One stream, no host synchronisation:
+        after one eager call (it fills the coefficient cache) the call records into a hipGraph without parallel branches."""
+        from .infer import ssd_head_offsets
+        self._check_input(x)
+        if not getattr(self, "converted", False):
+            raise RuntimeError("infer_converted: call hip_convert() first")
+        if self.model.training:
+            raise RuntimeError("this model was converted to int8 inference (hip_convert): it cannot be trained; rebuild the QAT model")
+        with torch.cuda.device(self.device):
+            sources = self._sources_converted(x)
+            n, C = sources[0].n, self.model.num_classes
+            anchors = list(self.model.ANCHORS)
+            offs = ssd_head_offsets(anchors, [(s.h, s.w) for s in sources])
+            p = offs[-1] + sources[-1].h * sources[-1].w * anchors[-1]
+            loc = torch.empty(n, p, 4, dtype=torch.float32, device=self.device)
+            conf = torch.empty(n, p, C, dtype=torch.float32, device=self.device)
+            for k, (s, layers) in enumerate(zip(sources, self.heads)):
+                self._head_converted(k, s, layers, loc, conf, offs[k], p)
+            self.E.tape = []
+        return loc, conf
 
     def forward_maps(self, x):
         self._check_input(x)

@@ -427,6 +427,28 @@ class SSDLiteFrostNet(_FrostBase):
         with torch.no_grad():
             return d(*self.hip_infer_bf16(x))
 
+    def hip_infer_int8(self, x):
+        """Inference of the hip_convert()-ed detector -> (loc [N,P,4], conf [N,P,C], priors), bit-equal to model(x): the heads of every source store their
+        dequantised fp32 values straight in _assemble's order (frostnet_amd.runner.SSDRunner.infer_converted; FROST_CVT_HEAD selects fused heads / layer launches); model(x) itself keeps the twelve-map form."""
+        if not self._is_qat_prepared() or not self.__dict__.get("_hip_converted", False):
+            raise RuntimeError("hip_infer_int8 is the converted detector's inference path: call hip_convert() on the QAT-prepared model first")
+        if self.training:
+            raise RuntimeError("int8 inference is the eval-mode graph: call model.eval() first")
+        with torch.no_grad():
+            loc, conf = self.hip_runner().infer_converted(x)
+        return loc, conf, self.priors
+
+    def hip_detect_int8(self, x, top_k=200, conf_thresh=0.01, nms_thresh=0.45):
+        """detect() on the converted detector's inference path: Detect(...)(*hip_infer_int8(x)) -> [N, num_classes, top_k, 5] with the Detect object detect() caches
+        (`last_counts` as there); equal to model.detect(x) bit for bit.  After one eager call the whole call records into a HIP graph on a static input."""
+        if not self._is_qat_prepared() or not self.__dict__.get("_hip_converted", False):
+            raise RuntimeError("hip_detect_int8 is the converted detector's inference path: call hip_convert() on the QAT-prepared model first")
+        if self.training:
+            raise RuntimeError("int8 inference is the eval-mode graph: call model.eval() first")
+        d = self._detect_layer(top_k, conf_thresh, nms_thresh)
+        with torch.no_grad():
+            return d(*self.hip_infer_int8(x))
+
     def hip_runner(self):
         """The device executor: SSDRunner (fake-quant) for the QAT-prepared model, FloatSSDRunner for the float model (StatAssist warm-up / float
         training, `float_precision` 'bf16' | 'fp32'); rebuilt when the mode, the float precision or the parameters change."""

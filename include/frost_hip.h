@@ -679,6 +679,30 @@ int frost_stem_converted(const float* x, int n, int h, int w, int64_t sn, int64_
                          const int8_t* wq_pack, const int32_t* wsum, const float* coef, const float* qrec_y, int cout, int mode, int8_t* y,
                          void* stream);
 int frost_avgpool_q(const int8_t* x, int n, int hw, int c, int32_t* pooled, void* stream);
+/* ---- prediction heads of the converted detector (csrc/frost_iheadq.hip; additive entries, ABI 5) ----
+ * replaces: per SSD source, quantized::conv2d_relu (depthwise 3x3) -> quantized::conv2d (1x1) of both SepHeads, DeQuantStub on both maps and the permute / slice /
+ * cat of SSDLiteFrostNet._assemble (ssdlite.py; the converted SSD of Object_Detection/qeval_convert.py) -- ONE launch that stores fp32 straight into the image rows.
+ * FrostCvtHead (a HOST struct) names one SepHead by its layers' own device arrays: dw_wq / dw_wsum = the depthwise layer's int8 taps [9][round_up(cin,16)] and
+ * tap sums, pw_wq / pw_wsum = the 1x1 layer's A-fragment pack and weight sums (frost_weight_prep), dw_coef / pw_coef = their coefficient rows after
+ * frost_conv_finalize_converted / _fb (the 1x1 layer's computed against dw_qy as its input record), dw_qy / pw_qy = their output records, cout = the 1x1 layer's
+ * channels (class padding included).
+ * x: NHWC offset-binary indices [n][h][w][cin] under qrec_x.  Stores loc[img * loc_stride + loc_off + pix * width_loc + j] (j < width_loc) and
+ * conf[img * conf_stride + conf_off + pix * width_conf + j] (j < width_conf), fp32 = (float)(index - zero_point) * scale of the head's record; channels
+ * width .. cout - 1 are computed and dropped; nothing else of loc / conf is written.  mode 2 / 3 = QNNPACK / FBGEMM requantisation as frost_pw_conv_fwd.
+ * The values are those of frost_dw_conv_fwd + frost_pw_conv_fwd (mode 2 / 3) + frost_dequant_act bit for bit.  frost_cvt_head_ok: 1 if the geometry is taken
+ * (cin a multiple of 8; at most ten 16-channel tiles over the two 1x1 layers). */
+typedef struct FrostCvtHead {
+  const int8_t* dw_wq; const int32_t* dw_wsum; const float* dw_coef; const float* dw_qy;
+  const int8_t* pw_wq; const int32_t* pw_wsum; const float* pw_coef; const float* pw_qy;
+  int32_t cout, reserved;
+} FrostCvtHead;
+int frost_cvt_head_ok(int h, int w, int cin, int cout_loc, int cout_conf);
+int frost_cvt_head(const int8_t* x, const float* qrec_x, const FrostCvtHead* loc_head, const FrostCvtHead* conf_head, int n, int h, int w, int cin,
+                   int width_loc, int width_conf, int mode, float* loc, int64_t loc_stride, int64_t loc_off, float* conf, int64_t conf_stride,
+                   int64_t conf_off, void* stream);
+/* the placement pass of the layer-launch form (geometries frost_cvt_head_ok refuses): y = one head map [n][hw][cout] (offset-binary indices under qrec_y);
+ * out[img * out_stride + out_off + pix * width + j] = (float)(index - zero_point) * scale for j < width <= cout.  No NCHW round trip, no cat. */
+int frost_cvt_place(const int8_t* y, const float* qrec_y, int n, int hw, int cout, int width, float* out, int64_t out_stride, int64_t out_off, void* stream);
 /* replaces: quantized::conv2d of the classifier (frostnet.py:298) + DeQuantStub: exact int32 GEMV, coefficient rows as above */
 int frost_classifier_q(const int32_t* pooled, const float* qrec_x, const int8_t* wq, const float* coef, int n, int c, int cout,
                        const float* qrec_y, float* logits, uint8_t* idx, void* stream);
