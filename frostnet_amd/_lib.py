@@ -250,6 +250,7 @@ _PROTOS = {
     "frost_head_bwd": [P, P, P, P, I, I, I, I, P, P, P, P, P, P, P],
     "frost_gradboost_step": [P, I, L, P, P, P, P, P],
     "frost_softmax_ce": [P, P, I, I, F, P, P, P],
+    "frost_softmax_ce_metrics": [P, P, I, I, F, I, P, P, P, P],
     "frost_dropout_mask": [P, C.c_uint64, L, F, P, P],
     "frost_conv_finalize_converted": [P, P, P, P, P, P, I, P, P, P],
     "frost_conv_finalize_converted_fb": [P, P, P, P, P, P, I, P, P, P],

@@ -521,6 +521,71 @@ extern "C" int frost_softmax_ce(const float* logits, const int64_t* target, int 
   hipLaunchKernelGGL(k_softmax_ce, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, as_stream(stream), logits, target, n, c, inv_n, loss, dlogits);
   return frost_check_launch("softmax_ce");
 }
+// replaces: the loss AND accuracy() of the epoch loops (helper_functions.py:32-46,145-155; harness._epoch's torch.topk + eq / sum / mul / stack / add after every
+// step): k_softmax_ce's pass plus the RANK of the target in its row, rank = #{j : x_j > x_t} + #{j < t : x_j == x_t} (equal logits: the lower class index
+// first), and the epoch's running sums.  record: FOUR doubles {sum of batch losses, sum of batch top-1 %, sum of batch top-k %, batches}: every row contributes
+// loss_row * inv_n and, on a hit (rank < 1 / rank < min(topk, c); an ignored target or a non-finite target logit is a miss for both), 100 * inv_n; the workgroup
+// of row 0 adds the batch.  The four rows of a workgroup are added up in row order first and leave in ONE atomic per sum (fp32 for `loss`, fp64 for the record):
+// up to 8 rows the loss is therefore the same bits in every run (two addends commute); the hit sums are exact in fp64 in any order.  dx is written with
+// k_softmax_ce's expressions (bit-equal).
+__global__ __launch_bounds__(256) void k_softmax_ce_metrics(const float* __restrict__ x, const int64_t* __restrict__ tgt, int n, int c, float inv_n, int topk,
+                                                            float* __restrict__ loss, float* __restrict__ dx, double* __restrict__ record) {
+  __shared__ float s_loss[4];
+  __shared__ int s_hit[4];          // bit 0: the row has a loss term, bit 1: top-1 hit, bit 2: top-k hit
+  const int wave = threadIdx.x >> 6, row = blockIdx.x * 4 + wave, lane = threadIdx.x & 63;
+  float lrow = 0.0f;
+  int flags = 0;
+  if (row < n) {                    // (uniform per wave)
+    const float* xr = x + (int64_t)row * c;
+    const int64_t t = tgt[row];
+    const bool valid = t >= 0 && t < c;
+    const float xt = valid ? xr[t] : 0.0f;
+    float m = -INFINITY;
+    int above = 0;
+    for (int k = lane; k < c; k += 64) {
+      const float v = xr[k];
+      m = fmaxf(m, v);
+      above += (v > xt || (v == xt && k < (int)t)) ? 1 : 0;
+    }
+    m = wave_max(m);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o);
+    float s = 0.0f;
+    for (int k = lane; k < c; k += 64) s += expf(xr[k] - m);
+    s = wave_sum(s);
+    if (dx) {
+      const float w = valid ? inv_n / s : 0.0f;
+      for (int k = lane; k < c; k += 64) dx[(int64_t)row * c + k] = expf(xr[k] - m) * w - ((valid && k == (int)t) ? inv_n : 0.0f);
+    }
+    if (valid) {
+      const bool finite = fabsf(xt) <= 3.402823466e38f;          // false for +-inf and NaN
+      lrow = (logf(s) + (m - xt)) * inv_n;          // lse - x_t with the difference of the two logits taken first: (m + log s) - x_t rounds at the logits' magnitude
+      flags = 1 | ((finite && above == 0) ? 2 : 0) | ((finite && above < (topk < c ? topk : c)) ? 4 : 0);
+    }
+  }
+  if (lane == 0) { s_loss[wave] = lrow; s_hit[wave] = flags; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  float lsum = 0.0f;
+  double dsum = 0.0;
+  int any = 0, h1 = 0, hk = 0;
+  for (int w = 0; w < 4; ++w) {
+    const int f = s_hit[w];
+    if (f & 1) { lsum += s_loss[w]; dsum += (double)s_loss[w]; any = 1; }
+    h1 += (f >> 1) & 1; hk += (f >> 2) & 1;
+  }
+  const double hit = 100.0 * (double)inv_n;
+  if (any) { atomicAdd(loss, lsum); atomicAdd(record + 0, dsum); }
+  if (h1) atomicAdd(record + 1, hit * (double)h1);
+  if (hk) atomicAdd(record + 2, hit * (double)hk);
+  if (blockIdx.x == 0) atomicAdd(record + 3, 1.0);
+}
+extern "C" int frost_softmax_ce_metrics(const float* logits, const int64_t* target, int n, int c, float inv_n, int topk, float* loss, float* dlogits,
+                                        double* record, void* stream) {
+  FROST_REQUIRE(n > 0 && c > 0 && topk >= 1 && logits && target && loss && record, "softmax_ce_metrics: n, c, topk >= 1; logits, target, loss and record must be given");
+  hipLaunchKernelGGL(k_softmax_ce_metrics, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, as_stream(stream), logits, target, n, c, inv_n, topk, loss, dlogits, record);
+  return frost_check_launch("softmax_ce_metrics");
+}
 
 // replaces: nn.Dropout's mask (frostnet.py:297) -- Bernoulli(keep) / keep per pooled feature, Philox4x32-10 keyed by `seed`, counter =
 // (element index, *draw): `draw` is a device-resident uint64 that the kernel's last thread advances, so a captured hipGraph draws a fresh

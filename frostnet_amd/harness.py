@@ -50,6 +50,113 @@ class CrossEntropyLoss(torch.nn.Module):
         return _CEFunction.apply(logits, target)
 
 
+class EpochMeter:
+    """The running sums of an epoch loop -- `record` = four doubles {sum of batch losses, sum of batch top-1 %, sum of batch top-k %, batches}, the sums `_epoch`
+    keeps (the mean over the iterations of per-batch values, so a short last batch weighs as it does there) -- accumulated by the loss kernel itself
+    (`frost_softmax_ce_metrics`) instead of `accuracy()`'s topk / eq / sum launches behind every step.  The definition, per row: rank of the target =
+    #{j : x_j > x_t} + #{j < t : x_j == x_t} (equal logits: the lower class index first, the convention of ssdlite.Detect); top-1 hit: rank == 0; top-k hit:
+    rank < min(topk, C); a row whose target is ignored (< 0) or whose target logit is not finite misses both; each row adds loss_row / N and 100 / N per hit.
+    On CPU tensors `update` runs that definition as torch code (the yardstick of the kernel's tests).  `reset()` is an asynchronous memset, `read()` the epoch's single
+    host read."""
+
+    def __init__(self, device, topk=5):
+        if int(topk) < 1:
+            raise ValueError("EpochMeter: topk >= 1")
+        self.device, self.topk = torch.device(device), int(topk)
+        self.record = torch.zeros(4, dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        self.record.zero_()
+
+    @staticmethod
+    def _check(logits, target):
+        if logits.dim() != 2 or target.dim() != 1 or target.dtype != torch.int64 or target.size(0) != logits.size(0) or logits.size(0) < 1 or logits.size(1) < 1:
+            raise ValueError("EpochMeter expects (N, C) logits and (N,) int64 class indices")
+
+    def _launch(self, x, target, dlogits):
+        """One launch: loss (returned, a new fp32 scalar), dlogits (may be None) and the record's sums."""
+        from ._lib import call, ptr, stream
+        if x.device != self.record.device or target.device != x.device:
+            raise ValueError(f"EpochMeter on {self.record.device}: logits on {x.device}, target on {target.device}")
+        n, c = x.shape
+        loss = torch.zeros((), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            call("frost_softmax_ce_metrics", ptr(x), ptr(target.contiguous()), n, c, 1.0 / n, self.topk, ptr(loss), ptr(dlogits), ptr(self.record), stream())
+        return loss
+
+    def update_reference(self, logits, target):
+        """The definition in fp64 torch code (any device): adds the batch to the record, returns the batch loss (fp64 scalar)."""
+        self._check(logits, target)
+        x, t = logits.detach().double(), target.to(logits.device)
+        n, c = x.shape
+        inv_n = float(torch.tensor(1.0 / n, dtype=torch.float32))              # the kernel's fp32 launch argument
+        valid = (t >= 0) & (t < c)
+        tc = t.clamp(0, c - 1)
+        xt = x.gather(1, tc[:, None])
+        rows = torch.where(valid, torch.logsumexp(x, 1) - xt[:, 0], torch.zeros_like(xt[:, 0]))
+        idx = torch.arange(c, device=x.device)
+        rank = ((x > xt) | ((x == xt) & (idx[None, :] < tc[:, None]))).sum(1)
+        ok = valid & torch.isfinite(xt[:, 0])
+        loss = rows.sum() * inv_n
+        hits1, hitsk = (ok & (rank == 0)).sum().double(), (ok & (rank < min(self.topk, c))).sum().double()
+        self.record += torch.stack([loss, hits1 * (100.0 * inv_n), hitsk * (100.0 * inv_n), torch.ones((), dtype=torch.float64, device=x.device)]).to(self.record.device)
+        return loss
+
+    def update(self, logits, target, loss=None):
+        """Adds a batch: the fused launch on the device, the torch definition on the CPU.  `loss` (a scalar tensor): the batch loss to record in place of the
+        cross-entropy of `logits` (a criterion of the caller's own).  Returns the loss that was recorded."""
+        if not logits.is_cuda:
+            before = self.record[0].clone()
+            ce = self.update_reference(logits, target)
+        else:
+            self._check(logits, target)
+            before = self.record[0].clone() if loss is not None else None
+            ce = self._launch(logits.detach().contiguous().float(), target, None)
+        if loss is None:
+            return ce
+        self.record[0] = before + loss.detach().double().reshape(())
+        return loss
+
+    def read(self):
+        """(mean loss, mean top-1 %, mean top-k %) over the batches seen since `reset()`: one device -> host read."""
+        loss, a1, ak, nb = self.record.tolist()
+        if nb == 0:
+            raise ValueError("EpochMeter.read: no batch since reset()")
+        return loss / nb, a1 / nb, ak / nb
+
+
+class _CEMetricsFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, meter):
+        x = logits.contiguous().float()
+        dlogits = torch.empty_like(x) if ctx.needs_input_grad[0] else None            # validation under no_grad: loss and metrics only
+        loss = meter._launch(x, target, dlogits)
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * g, None, None
+
+
+class CrossEntropyWithMetrics(torch.nn.Module):
+    """`CrossEntropyLoss` (same contract: (N, C) fp32 logits, (N,) int64 targets, loss and dlogits from one launch, capturable) whose launch also adds the batch's
+    loss, top-1 and top-k hits to `meter` (an `EpochMeter`).  Works under `torch.no_grad()` (no dlogits) and as `parallel.SegmentedStep`'s criterion."""
+
+    def __init__(self, meter):
+        super().__init__()
+        self.meter = meter
+
+    def forward(self, logits, target):
+        if not logits.is_cuda:
+            self.meter.update_reference(logits, target)
+            return torch.nn.functional.cross_entropy(logits, target, reduction="sum") / logits.size(0)
+        if target.dtype != torch.int64 or target.dim() != 1 or logits.dim() != 2:
+            raise ValueError("CrossEntropyWithMetrics expects (N, C) logits and (N,) int64 class indices")
+        return _CEMetricsFunction.apply(logits, target, self.meter)
+
+
 def make_param_groups(model, weight_decay):
     groups = []
     others = weight_decay * 0.01
@@ -146,17 +253,24 @@ def _epoch(loader, model, criterion, optimizer, epoch, args, grad_sync, train_mo
     return loss, a1, a5
 
 
-def train(train_loader, model, criterion, optimizer, epoch, total_ep=None, args=None, grad_sync=None, transform=None):
+def train(train_loader, model, criterion, optimizer, epoch, total_ep=None, args=None, grad_sync=None, transform=None, graph=False):
     """One training epoch (helper_functions.py:99-163): returns (mean loss, mean top-1, mean top-5) over the iterations.  With a `transform` (a
-    `ClassificationAugmentation`) the loader yields (images uint8, sizes, target) in `pad_images`' format and the transform turns them into the model's input on the device."""
+    `ClassificationAugmentation`) the loader yields (images uint8, sizes, target) in `pad_images`' format and the transform turns them into the model's input on the device.
+    `graph`: True drives a `GraphedStep` made for this call (the iteration replayed as one hipGraph, loss and accuracies summed by the loss kernel into an `EpochMeter`);
+    pass a `GraphedStep` of your own so that the capture survives across epochs."""
     model.train()
+    if graph is not False and graph is not None:
+        return _epoch_graphed(train_loader, _graphed(graph, model, criterion, optimizer, transform, grad_sync), epoch, args, True)
     return _epoch(train_loader, model, criterion, optimizer, epoch, args, grad_sync, True, transform)
 
 
-def val(val_loader, model, criterion, transform=None):
+def val(val_loader, model, criterion, transform=None, graph=False):
     """One validation pass (helper_functions.py:306-350): `model.eval()` only -- BatchNorm uses its running statistics while every FakeQuantize
-    observer that has not been disabled explicitly keeps updating, exactly as the reference's val() leaves them.  `transform` (a `ClassificationEvalTransform`): as in `train`."""
+    observer that has not been disabled explicitly keeps updating, exactly as the reference's val() leaves them.  `transform` (a `ClassificationEvalTransform`): as in `train`.
+    `graph`: as in `train` (a `GraphedStep` without an optimizer)."""
     model.eval()
+    if graph is not False and graph is not None:
+        return _epoch_graphed(val_loader, _graphed(graph, model, criterion, None, transform, None), 0, None, False)
     return _epoch(val_loader, model, criterion, None, 0, None, None, False, transform)
 
 
@@ -188,6 +302,359 @@ def val_detector(loader, model, evaluator, top_k=200, conf_thresh=0.01, nms_thre
     if vals[0] != 0:
         raise RuntimeError(evaluator.OVERFLOW_MSG)
     return vals[1], vals[2:]
+
+
+def _is_plain_ce(criterion):
+    if isinstance(criterion, CrossEntropyLoss):
+        return True
+    return (type(criterion) is torch.nn.CrossEntropyLoss and criterion.weight is None and criterion.reduction == "mean" and criterion.ignore_index == -100
+            and getattr(criterion, "label_smoothing", 0.0) == 0.0)
+
+
+class _Captured:
+    """One captured input signature of a GraphedStep: static inputs, their staging buffers, the graph(s) and what they were captured against."""
+    __slots__ = ("statics", "staging", "graph", "seg", "plan", "runner", "training", "logits", "staged", "free", "rows", "dp_in")
+
+
+class GraphedStep:
+    """One loop iteration as a replayed hipGraph -- what `bench.py` times, for the loops a user calls.
+
+    `step(*batch) -> loss` (a persistent device scalar; nothing synchronises with the host).  With an `optimizer` it is a training iteration (transform -> zero_grad ->
+    forward -> loss -> backward -> optimizer launch), without one a validation forward under `no_grad`.  `batch` is what the loader yields: classifier `(inp, target)`, or
+    `(images, sizes, target)` with a `transform` (`ClassificationAugmentation` / `ClassificationEvalTransform`); detector (`criterion` is a `ssdlite.MultiBoxLoss`)
+    `(images, boxes, valid)`, or `(images, sizes, boxes, valid)` with a `transform` (`SSDAugmentation`).
+
+    The first `eager_warmup` calls of an input signature (shapes and dtypes) run eagerly (descriptor tables, optimizer state, coefficient caches); the next one captures the
+    iteration on a side stream (`optimizer.prepare_step()` in front of the capture, `optimizer.launch(plan)` inside it); later calls copy the batch into the graph's static
+    inputs, call `optimizer.prepare_step()` and replay.  A pinned host batch travels on a copy stream into a staging buffer while the previous replay runs and from there
+    in-stream into the static input; a device batch is copied in-stream.  Graphs exist for at most two signatures (the full batch and a smaller last one); anything else runs
+    eagerly.  Live at every replay because they stay outside the graph: per-group lr / weight_decay and `is_warmup` (uploaded by `prepare_step`), the Philox offset, the
+    augmentation and dropout stream positions (device words).  The step is captured AGAIN, never replayed stale, when the model's runner is no longer valid, when the
+    optimizer's plan changed (`load_state_dict`, `add_param_group`) or when `model.training` differs from the capture.
+
+    Data parallel (`group` given, or a default process group of more than one rank): the body is `parallel.SegmentedStep` (capture / replay / finish, then the optimizer
+    launch); collectives are never captured.  A float model (StatAssist warm-up: `FloatRunner`, `FloatSSDRunner`), a CPU model and an optimizer without `prepare_step` /
+    `launch` run the same iteration eagerly (the float step measured slower replayed than eager) -- still with the fused metrics.
+
+    Classifier metrics go to `meter` (an `EpochMeter`: the criterion's own when it is a `CrossEntropyWithMetrics`; a plain cross-entropy criterion is replaced by one); the
+    logits of the last iteration are `logits`.  Detector: `record` = three device doubles {sum loss_l, sum loss_c, batches}, `loss_terms` = the last (loss_l, loss_c)."""
+
+    def __init__(self, model, criterion, optimizer=None, transform=None, nbuckets=4, group=None, eager_warmup=2):
+        from .ssdlite import MultiBoxLoss
+        self.model, self.optimizer, self.transform, self.nbuckets, self.group = model, optimizer, transform, nbuckets, group
+        self.eager_warmup = max(int(eager_warmup), 1 if optimizer is not None else 0)          # the optimizer's table is built from the gradients of a first eager step
+        self.device = dev = _device_of(model)
+        self.detector = isinstance(criterion, MultiBoxLoss)
+        self.meter, self.record, self.loss_terms, self._own_loss = None, None, None, False
+        if self.detector:
+            self.criterion = criterion
+            self.record = torch.zeros(3, dtype=torch.float64, device=dev)
+            self.loss_terms = torch.zeros(2, dtype=torch.float32, device=dev)
+        elif isinstance(criterion, CrossEntropyWithMetrics):
+            self.criterion, self.meter = criterion, criterion.meter
+        elif _is_plain_ce(criterion):
+            self.meter = EpochMeter(dev)
+            self.criterion = CrossEntropyWithMetrics(self.meter)
+        else:                                         # a criterion of the caller's own: its loss is recorded, the hits come from one metrics-only launch
+            self.criterion, self.meter, self._own_loss = criterion, EpochMeter(dev), True
+        self.loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.logits = None
+        self.capture = True                           # False: the same iteration with eager launches throughout
+        self.captures = 0                             # how many times a graph was captured (tests, tools)
+        self._graphs, self._seen, self._copy_stream, self._seg_eager = {}, {}, None, None
+
+    # ---- what is captured ----
+    def _data_parallel(self):
+        if self.optimizer is None:
+            return False
+        import torch.distributed as dist
+        return self.group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+
+    def _capturable(self):
+        m, o = self.model, self.optimizer
+        if self.device.type != "cuda" or not hasattr(m, "hip_runner") or not m._is_qat_prepared() or getattr(m, "_hip_converted", False):
+            return False
+        return o is None or (hasattr(o, "prepare_step") and hasattr(o, "launch"))
+
+    def graph_for(self, *batch):
+        """The captured graph object of this batch's signature (None while it runs eagerly; a list of segment graphs on the data-parallel path)."""
+        g = self._graphs.get(self._signature(batch))
+        return None if g is None else (g.graph if g.seg is None else g.seg.graphs)
+
+    @staticmethod
+    def _signature(batch):
+        return tuple((tuple(t.shape), t.dtype) for t in batch)
+
+    def _split(self, batch):
+        """-> (model input, target) from a device batch; the transform runs here, in front of the model."""
+        if self.detector:
+            if self.transform is None:
+                images, boxes, valid = batch
+                return images, (boxes, valid)
+            images, sizes, boxes, valid = batch
+            x, boxes, valid = self.transform(images, sizes, boxes, valid)
+            return x, (boxes, valid)
+        if self.transform is None:
+            return batch
+        images, sizes, target = batch
+        return self.transform(images, sizes), target
+
+    def _record_detector(self, ll, lc):
+        terms = torch.stack([ll.detach(), lc.detach()]).float()
+        self.loss_terms.copy_(terms)
+        self.record[:2] += terms.double()
+        self.record[2] += 1.0
+
+    def _loss_of(self, out, target):
+        if self.detector:
+            ll, lc = self.criterion(out, target)
+            self._record_detector(ll, lc)
+            return ll + lc
+        loss = self.criterion(out, target)
+        if self._own_loss:
+            self.meter.update(out, target, loss=loss)
+        return loss
+
+    def _forward_backward(self, batch):
+        """The iteration without its optimizer step, from a device batch (eager, or recorded into a capture)."""
+        x, target = self._split(batch)
+        if self.optimizer is None:
+            with torch.no_grad():
+                out = self.model(x)
+                loss = self._loss_of(out, target)
+        else:
+            self.optimizer.zero_grad(set_to_none=True)
+            out = self.model(x)
+            loss = self._loss_of(out, target)
+            loss.backward()
+        self.loss.copy_(loss.detach().reshape(()))
+        return None if self.detector else out.detach()
+
+    # ---- data parallel: parallel.SegmentedStep is the body ----
+    def _segmented(self):
+        from .parallel import SegmentedStep
+        runner = self.model.hip_runner()
+        if self.detector:
+            def maps_loss(maps, target):
+                ll, lc = self.criterion(self.model._assemble(maps), target)
+                self._record_detector(ll, lc)
+                return ll + lc
+            return SegmentedStep(runner, nbuckets=self.nbuckets, group=self.group, maps_loss=maps_loss)
+        if self._own_loss:
+            def crit(logits, target):
+                loss = self.criterion(logits, target)
+                self.meter.update(logits, target, loss=loss)
+                return loss
+            return SegmentedStep(runner, crit, nbuckets=self.nbuckets, group=self.group)
+        return SegmentedStep(runner, self.criterion, nbuckets=self.nbuckets, group=self.group)
+
+    def _eager_segmented(self, batch):
+        if self._seg_eager is None or self._seg_eager.runner is not self.model.hip_runner():
+            self._seg_eager = self._segmented()
+        x, target = self._split(batch)
+        self.loss.copy_(self._seg_eager.run_eager(x, target))
+        self._seg_eager.finish()
+        self.optimizer.step()
+        self.logits = None
+        return self.loss
+
+    # ---- eager ----
+    def _to_device(self, batch):
+        return tuple(t.to(self.device, non_blocking=True) for t in batch)
+
+    def _eager(self, batch):
+        batch = self._to_device(batch)
+        if self.optimizer is not None and not self.model.training:
+            raise RuntimeError("GraphedStep with an optimizer is a training iteration: call model.train() first")
+        if self._data_parallel():
+            if not self._capturable():
+                raise NotImplementedError("GraphedStep: the data-parallel body (parallel.SegmentedStep) binds the fake-quantised model on the device; run this model "
+                                          "through train(..., graph=False, grad_sync=...)")
+            return self._eager_segmented(batch)
+        self.logits = self._forward_backward(batch)
+        if self.optimizer is not None:
+            self.optimizer.step()
+        return self.loss
+
+    # ---- input copy ----
+    def _load(self, g, batch):
+        cur = torch.cuda.current_stream(self.device)
+        host = [i for i, t in enumerate(batch) if not t.is_cuda]
+        if host:
+            if self._copy_stream is None:
+                self._copy_stream = torch.cuda.Stream(device=self.device)
+            cs = self._copy_stream
+            if g.free is not None:
+                cs.wait_event(g.free)                 # the previous in-stream copy has read the staging buffers
+            with torch.cuda.stream(cs):
+                for i in host:
+                    g.staging[i].copy_(batch[i], non_blocking=True)          # (a pinned batch: asynchronous, beside the previous replay)
+            g.staged.record(cs)
+            cur.wait_event(g.staged)
+        for i, t in enumerate(batch):
+            g.statics[i].copy_(g.staging[i] if not t.is_cuda else t, non_blocking=True)
+        if host:
+            if g.free is None:
+                g.free = torch.cuda.Event()
+            g.free.record(cur)
+
+    # ---- capture / replay ----
+    def _capture(self, sig, batch, plan):
+        dev = self.device
+        g = _Captured()
+        g.statics = [torch.empty(t.shape, dtype=t.dtype, device=dev) for t in batch]
+        g.staging = [None if t.is_cuda else torch.empty(t.shape, dtype=t.dtype, device=dev) for t in batch]
+        g.staged, g.free, g.graph, g.seg, g.logits, g.dp_in, g.rows = torch.cuda.Event(), None, None, None, None, None, batch[0].size(0)
+        g.runner, g.training, g.plan = self.model.hip_runner(), self.model.training, plan
+        self._load(g, batch)
+        import torch.distributed as dist
+        with torch.cuda.device(dev):
+            if self._data_parallel():
+                g.seg = self._segmented()
+                x, target = self._split(tuple(g.statics))          # the transform stays in front of the segments: launched in-stream at every step
+                g.dp_in = (x,) + (tuple(target) if isinstance(target, tuple) else (target,))
+                g.seg.capture(x, target)
+            else:
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(side):
+                    g.graph = torch.cuda.CUDAGraph()
+                    # (a process group's watchdog thread polls events concurrently: restrict the capture check to this thread when one exists)
+                    with torch.cuda.graph(g.graph, stream=side, capture_error_mode="thread_local" if dist.is_available() and dist.is_initialized() else "global"):
+                        g.logits = self._forward_backward(tuple(g.statics))
+                        if self.optimizer is not None:
+                            self.optimizer.launch(plan)
+                torch.cuda.current_stream(dev).wait_stream(side)
+        self.captures += 1
+        self._graphs[sig] = g
+        return g
+
+    def _replay(self, g, captured_now=False):
+        if g.seg is not None:
+            if self.transform is not None and not captured_now:            # the segments read the transform's output where the capture left it (and just made it)
+                x, target = self._split(tuple(g.statics))
+                for dst, src in zip(g.dp_in, (x,) + (tuple(target) if isinstance(target, tuple) else (target,))):
+                    if dst is not src:
+                        dst.copy_(src)
+            g.seg.replay()
+            g.seg.finish()
+            self.optimizer.launch(g.plan)
+            self.loss.copy_(g.seg.loss)
+        else:
+            g.graph.replay()
+        self.logits = g.logits
+        return self.loss
+
+    def step(self, *batch):
+        if not self.capture or not self._capturable():
+            return self._eager(batch)
+        if self.optimizer is not None and not self.model.training:
+            raise RuntimeError("GraphedStep with an optimizer is a training iteration: call model.train() first (the training graph is never replayed in eval mode)")
+        sig = self._signature(batch)
+        runner = self.model.hip_runner()
+        if any(c.runner is not runner for c in self._graphs.values()):          # parameters or buffers moved: every graph holds stale pointers, and the new runner starts cold
+            self._graphs.clear()
+            self._seen.clear()
+        g = self._graphs.get(sig)
+        if g is not None and g.training != self.model.training:
+            del self._graphs[sig]
+            g = None
+        rows = batch[0].size(0)
+        if g is None:
+            seen = self._seen.get(sig, 0)
+            # a second graph only for a batch no larger than the first one's (the last, partial batch): the engine grows some work buffers on demand, and a
+            # larger batch would replace them under the graph that was captured with them -- such a batch runs eagerly, and the graphs are captured again after it
+            fits = all(rows <= c.rows for c in self._graphs.values())
+            if seen < self.eager_warmup or len(self._graphs) >= 2 or not fits:
+                self._seen[sig] = seen + 1
+                if not fits:
+                    self._graphs.clear()
+                return self._eager(batch)
+            plan = self.optimizer.prepare_step() if self.optimizer is not None else None
+            g = self._capture(sig, batch, plan)
+            return self._replay(g, captured_now=True)
+        self._load(g, batch)
+        if self.optimizer is not None:
+            plan = self.optimizer.prepare_step()
+            if plan is not g.plan:                    # load_state_dict / add_param_group: the captured launch reads the old table
+                del self._graphs[sig]
+                return self._replay(self._capture(sig, batch, plan), captured_now=True)
+        return self._replay(g)
+
+    __call__ = step
+
+    # ---- the detector's record ----
+    def reset_record(self):
+        (self.record if self.detector else self.meter.record).zero_()
+
+    def read_record(self):
+        """Detector: (mean loss_l, mean loss_c) over the iterations since `reset_record()`; classifier: the meter's triple.  One host read."""
+        if not self.detector:
+            return self.meter.read()
+        sl, sc, nb = self.record.tolist()
+        if nb == 0:
+            raise ValueError("GraphedStep.read_record: no iteration since reset_record()")
+        return sl / nb, sc / nb
+
+
+def _graphed(graph, model, criterion, optimizer, transform, grad_sync):
+    if grad_sync is not None:
+        raise ValueError("graph=True exchanges the gradients itself (parallel.SegmentedStep between the graph's segments): pass a GraphedStep(..., group=...) "
+                         "instead of grad_sync")
+    if isinstance(graph, GraphedStep):
+        if graph.model is not model or graph.optimizer is not optimizer or graph.transform is not transform:
+            raise ValueError("graph=<GraphedStep>: it was built for another model, optimizer or transform")
+        return graph
+    return GraphedStep(model, criterion, optimizer, transform)
+
+
+def _epoch_graphed(loader, step, epoch, args, train_mode):
+    step.reset_record()
+    n = 0
+    for i, batch in enumerate(loader):
+        if train_mode and args is not None and getattr(args, "lrsch", "cos_lr") == "cos_lr" and hasattr(args, "dataset_len"):
+            adjust_learning_rate_cosine(step.optimizer, epoch, i, args.dataset_len, args)
+        step(*batch)
+        n += 1
+    if n == 0:
+        raise ValueError("empty loader")
+    return step.read_record()                      # the epoch's single device -> host read
+
+
+def train_detector(loader, model, criterion, optimizer, start_iter, max_iter, lr, gamma, lr_steps, transform=None, graph=False):
+    """The detector's training loop (Object_Detection/qtrainval.py:259-304), driven by the iteration count: iterations start_iter .. max_iter - 1, the learning rate set
+    to lr * gamma^step_index at every entry of `lr_steps` (:270-272, adjust_learning_rate :336-344), the loader restarted whenever it is exhausted.  The loader yields
+    (images, boxes, valid) (ssdlite.pad_targets' format), or (images uint8, sizes, boxes, valid) for a `transform` (an `SSDAugmentation`, on the device in front of the
+    model).  `graph`: False = eager launches, True = a `GraphedStep` made here, or a `GraphedStep` of the caller's so that the capture survives across calls.  Returns the
+    mean (loss_l, loss_c) over the iterations from one host read."""
+    model.train()
+    if isinstance(graph, GraphedStep):
+        step = _graphed(graph, model, criterion, optimizer, transform, None)
+    else:
+        step = GraphedStep(model, criterion, optimizer, transform)
+        step.capture = bool(graph)
+    if not step.detector:
+        raise ValueError("train_detector: criterion must be a ssdlite.MultiBoxLoss")
+    step.reset_record()
+    step_index = sum(1 for s in lr_steps if s < start_iter)
+    it_loader = None
+    for iteration in range(start_iter, max_iter):
+        if iteration in lr_steps:
+            step_index += 1
+            for group in optimizer.param_groups:
+                group["lr"] = lr * (gamma ** step_index)
+        try:
+            if it_loader is None:
+                it_loader = iter(loader)
+            batch = next(it_loader)
+        except StopIteration:
+            it_loader = iter(loader)
+            try:
+                batch = next(it_loader)
+            except StopIteration:
+                raise ValueError("empty loader") from None
+        step(*batch)
+    return step.read_record()
 
 
 def checkpoint_state(model, optimizer, epoch, **scalars):

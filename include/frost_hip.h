@@ -648,6 +648,13 @@ int frost_block_bwd(const FrostBlockDesc* d, const FrostBlockBwd* b, void* strea
  * replaces: nn.CrossEntropyLoss(reduction='mean') forward + backward (Classification/train.py:147, helper_functions.py:140-142).
  * loss: one float (caller zeroes it; accumulated with atomics); dlogits = (softmax - onehot) * inv_n (may be NULL); target < 0 ignored. */
 int frost_softmax_ce(const float* logits, const int64_t* target, int n, int c, float inv_n, float* loss, float* dlogits, void* stream);
+/* The same loss and dlogits (dlogits bit-equal, may be NULL) plus the epoch loops' accuracy() and running sums in the same launch
+ * (helper_functions.py:32-46,145-155).  The target's rank in its row = #{j : x_j > x_t} + #{j < t : x_j == x_t} (equal logits: the lower class
+ * index first); top-1 hit: rank == 0, top-k hit: rank < min(topk, c); a row whose target is ignored or whose target logit is not finite misses both.
+ * record: FOUR device doubles {sum of batch losses, sum of batch top-1 %, sum of batch top-k %, batches}: every row adds loss_row * inv_n and, on a
+ * hit, 100 * inv_n (fp64 atomics, the four rows of a workgroup added up first); one lane of the launch adds 1 to `batches`.  The caller zeroes `loss` per launch and `record` per epoch. */
+int frost_softmax_ce_metrics(const float* logits, const int64_t* target, int n, int c, float inv_n, int topk, float* loss, float* dlogits,
+                             double* record, void* stream);
 /* replaces: nn.Dropout's Bernoulli mask on the pooled features (frostnet.py:297): out[i] in {0, 1/keep}, Philox4x32-10, counter =
  * (index, draw_counter[0]); draw_counter = TWO device-resident uint64 {draw, arrival ticket (zero)}: the last workgroup to finish advances the
  * draw counter itself (hipGraph replays draw fresh masks).  out: 16-byte aligned. */
