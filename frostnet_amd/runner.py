@@ -65,8 +65,6 @@ class _QATFeatFunction(torch.autograd.Function):
 def dropout_seed():
     """Philox key of the dropout masks: torch's seed (torch.manual_seed is honoured, Classification/train.py:38-39) mixed with the data-parallel
     rank, so that the ranks of one job draw different masks for their shards."""
-    import os
-    rank = 0
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         rank = torch.distributed.get_rank()
     else:
@@ -119,6 +117,9 @@ def _is_fused_fq(fq):
 
 
 class FrostRunner:
+    converted = False        # hip_convert() ran: forward() computes the converted int8 model (class-level defaults: for_block builds a runner without __init__)
+    converted_fb = False     # ... in the FBGEMM engine's form (a per-channel model)
+
     def __init__(self, model):
         L.load_library()   # raises if the HIP library is missing: no CPU fallback on the device path
         self.model = model
@@ -147,13 +148,17 @@ class FrostRunner:
         r.E, r.qa, r.rule127 = Engine(r.device), QArena(32, r.device), False
         r.block = r._bind_block("B", block)
         r.E.rule127 = 1 if r.rule127 else 0
-        r._params = list(block.parameters())
-        r.grad_arena = torch.zeros(sum(p.numel() for p in r._params), dtype=torch.float32, device=r.device)
-        r._grad_views, off = [], 0
-        for p in r._params:
-            r._grad_views.append(r.grad_arena[off: off + p.numel()].view_as(p))
-            off += p.numel()
+        r._make_grad_arena(list(block.parameters()))
         return r
+
+    def _make_grad_arena(self, params):
+        """Flat gradient arena, parameter order = model.parameters() (the reference's registration order)."""
+        self.grad_arena = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=self.device)
+        self._grad_views, off = [], 0
+        for p in params:
+            self._grad_views.append(self.grad_arena[off: off + p.numel()].view_as(p))
+            off += p.numel()
+        self._params = params
 
     def read_flags(self):
         """ONE device -> host read of the enable-flag columns of the qrecord arena (the torch `observer_enabled` / `fake_quant_enabled` buffers are
@@ -279,8 +284,7 @@ class FrostRunner:
         if pc:
             self._bind_weight_per_channel(m.weight_fake_quant, qw, l)
         l.bn_mod = m.bn
-        l.qmod = m                # the QAT module this layer executes (export_converted walks the module tree)
-        l.hswish = None
+        l.qmod = m
         act = getattr(blk, "act", None)
         if act is not None and type(act).__name__ == "Hswish":
             # ConvBNHswish (frostnet.py surface of the reference's `_ConvBNHswish`): the conv emits as a linear ConvBn2d with its own output FakeQuantize, then
@@ -364,14 +368,7 @@ class FrostRunner:
         self.E.rule127 = 1 if self.rule127 else 0
         # buffers were re-pointed: refresh the validity signature
         self._sig = tuple(p.data_ptr() for p in m.parameters()) + tuple(b.data_ptr() for b in m.buffers())
-        # flat gradient arena, parameter order = model.parameters() (the reference's registration order)
-        params = list(m.parameters())
-        self.grad_arena = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=self.device)
-        self._grad_views, off = [], 0
-        for p in params:
-            self._grad_views.append(self.grad_arena[off: off + p.numel()].view_as(p))
-            off += p.numel()
-        self._params = params
+        self._make_grad_arena(list(m.parameters()))
 
     def _bind_extra(self):
         """Subclasses bind further layers here (SSDRunner: extras + prediction heads)."""
@@ -427,7 +424,7 @@ class FrostRunner:
         the converted model computes on the QNNPACK engine -- int8 weights frozen at convert time, integer bias, fp32 requantisation,
         QNNPACK's fixed-point add, rounding average pool -- instead of the fake-quant eval graph (whose observers keep moving and whose
         pooled features are not re-quantised; the two differ by 8-25 % of the activations' indices, see tests/test_gpu_convert.py)."""
-        if getattr(self, "converted", False):
+        if self.converted:
             return self                          # idempotent: a second convert() must not move the weight observers again
         pcs = [l.per_channel for l in self.E.layers]
         if any(pcs) and not all(pcs):
@@ -445,7 +442,7 @@ class FrostRunner:
 
     def _trunk_converted(self, x, taps=None):
         """QuantStub + stem + every bottleneck of the converted model; returns (last activation, [block outputs])."""
-        E, fb = self.E, getattr(self, "converted_fb", False)
+        E, fb = self.E, self.converted_fb
         if x.dtype != torch.float32:
             x = x.float()
         a = E.stem_converted(self.stem, x, self.q_in, fb)
@@ -481,7 +478,7 @@ class FrostRunner:
 
     def _forward_converted(self, x, taps=None):
         a, _ = self._trunk_converted(x, taps)
-        fb = getattr(self, "converted_fb", False)
+        fb = self.converted_fb
         a = self.E.conv_converted(self.last, a, fb)
         logits = self.E.head_converted(self.cls, a, fb)
         self.E.tape = []
@@ -502,11 +499,11 @@ class FrostRunner:
         dtypes are those of stock torch, so the CPU model `torch.quantization.convert(prepare_qat(fuse_model(FrostNet(...))).eval())` loads it with
         load_state_dict(strict=True) and computes the device's logits bit for bit (tests/test_gpu_convert.py)."""
         from collections import OrderedDict
-        if not getattr(self, "converted", False):
+        if not self.converted:
             raise RuntimeError("export_converted: call hip_convert() first (torch.quantization.convert precedes state_dict() in the reference)")
         E = self.E
         E._ensure_tables()
-        by_mod = {id(l.qmod): (i, l) for i, l in enumerate(E.layers) if getattr(l, "qmod", None) is not None}
+        by_mod = {id(l.qmod): (i, l) for i, l in enumerate(E.layers) if l.qmod is not None}
         sd = OrderedDict()
 
         def qparams(fq, shape):
@@ -539,6 +536,10 @@ class FrostRunner:
                     sd[pre + "scale"], sd[pre + "zero_point"] = qparams(mod.activation_post_process, ())
         return sd
 
+    def _refuse_training(self):
+        if self.model.training:
+            raise RuntimeError("this model was converted to int8 inference (hip_convert): it cannot be trained; rebuild the QAT model")
+
     def _check_input(self, x):
         if x.device != self.device:
             raise RuntimeError(f"input is on {x.device} but the model's parameters (and its HIP runner) are on {self.device}")
@@ -549,9 +550,8 @@ class FrostRunner:
     def forward(self, x):
         self._check_input(x)
         training = self.model.training
-        if getattr(self, "converted", False):
-            if training:
-                raise RuntimeError("this model was converted to int8 inference (hip_convert): it cannot be trained; rebuild the QAT model")
+        if self.converted:
+            self._refuse_training()
             with torch.cuda.device(self.device):
                 return self._forward_converted(x)
         with torch.cuda.device(self.device):          # kernels launch on the CURRENT device's stream: make it the model's
@@ -576,7 +576,7 @@ class FrostRunner:
         if _PREP_SIDE and training and not E.grad_fp32:
             # the per-step weight preparation (BN fold + weight fake-quant + packing of all 70 layers: a handful of latency-bound launches, ~165 us) has nothing to do
             # with the image: it runs on a second stream beside the QuantStub's passes over the input (range, observer, quantise: ~115 us of bandwidth), joined before conv1
-            if getattr(E, "_prep_stream", None) is None:
+            if E._prep_stream is None:
                 E._prep_stream = torch.cuda.Stream(device=E.device)
             # (as ONE part: in the captured step the whole preparation costs 0.28 ms although it runs beside the QuantStub -- FROST_ABL_SKIP, profiles/r06_pricing.txt --
             # but keeping the layers from layer3 on under the high-resolution forward and joining them in front of layer3.0 measured +-0, profiles/r06_prologue_ab.txt)
@@ -585,7 +585,7 @@ class FrostRunner:
             with torch.cuda.stream(E._prep_stream):
                 E.begin_step(observe=obs)
             a = E.quantize_input(x, self.q_in, observe=obs)
-            if _STEM_COL_EARLY and self.stem.kind == "stem" and getattr(E, "trace", None) is None:
+            if _STEM_COL_EARLY and self.stem.kind == "stem" and E.trace is None:
                 a = E.stem_im2col(a)          # needs no weights: in front of the join (the join used to hold it back by the tail of the weight preparation)
             cur.wait_stream(E._prep_stream)
         else:
@@ -600,9 +600,8 @@ class FrostRunner:
 
     def forward_features(self, x):
         self._check_input(x)
-        if getattr(self, "converted", False):
-            if self.model.training:
-                raise RuntimeError("this model was converted to int8 inference (hip_convert): it cannot be trained; rebuild the QAT model")
+        if self.converted:
+            self._refuse_training()
             with torch.cuda.device(self.device):
                 return [a.dequant().contiguous() for a in self._features_converted(x)]
         with torch.cuda.device(self.device):
@@ -615,10 +614,7 @@ class FrostRunner:
         if x.dtype != torch.float32:
             x = x.float()
         _, feats = self._trunk(x, self.model.training)
-        ends, i = [], 0
-        for lname in ("layer1", "layer2", "layer3", "layer4", "layer5"):
-            i += len(getattr(self.model, lname))
-            ends.append(feats[i - 1])
+        ends = self._stage_ends(feats)
         if not record:
             self.E.tape = []
         return [ends[0], ends[1], ends[2], ends[4]]          # x4 is skipped (frostnet_features.py:350)
@@ -689,7 +685,7 @@ class SSDRunner(FrostRunner):
 
     def _sources_converted(self, x):
         """The six source activations of the converted detector: stage ends 1, 2 and 4 (0-based) of the trunk, then the output of every extra stage."""
-        E, fb = self.E, getattr(self, "converted_fb", False)
+        E, fb = self.E, self.converted_fb
         a, feats = self._trunk_converted(x)
         ends = self._stage_ends(feats)
         sources = [ends[1], ends[2], ends[4]]
@@ -701,7 +697,7 @@ class SSDRunner(FrostRunner):
     def _maps_converted(self, x):
         """The converted detector (Object_Detection/qeval_convert.py: torch.quantization.convert of the QAT SSD): backbone, extras and the separable
         prediction heads as quantized convs with the requantisation epilogue; twelve maps."""
-        E, fb = self.E, getattr(self, "converted_fb", False)
+        E, fb = self.E, self.converted_fb
         sources = self._sources_converted(x)
         maps = []
         for s, (ldw, lpw, cdw, cpw) in zip(sources, self.heads):
@@ -719,7 +715,7 @@ class SSDRunner(FrostRunner):
 
     def _head_converted(self, k, s, layers, loc, conf, poff, p):
         """Both SepHeads of source k into their region of the image rows of loc [N,P,4] / conf [N,P,C] (infer.ssd_head_offsets)."""
-        E, fb = self.E, getattr(self, "converted_fb", False)
+        E, fb = self.E, self.converted_fb
         ldw, lpw, cdw, cpw = layers
         A, C = self.model.ANCHORS[k], self.model.num_classes
         if self._cvt_head_fused(k, s, lpw, cpw):
@@ -747,10 +743,9 @@ class SSDRunner(FrostRunner):
         after one eager call (it fills the coefficient cache) the call records into a hipGraph without parallel branches."""
         from .infer import ssd_head_offsets
         self._check_input(x)
-        if not getattr(self, "converted", False):
+        if not self.converted:
             raise RuntimeError("infer_converted: call hip_convert() first")
-        if self.model.training:
-            raise RuntimeError("this model was converted to int8 inference (hip_convert): it cannot be trained; rebuild the QAT model")
+        self._refuse_training()
         with torch.cuda.device(self.device):
             sources = self._sources_converted(x)
             n, C = sources[0].n, self.model.num_classes
@@ -766,9 +761,8 @@ class SSDRunner(FrostRunner):
 
     def forward_maps(self, x):
         self._check_input(x)
-        if getattr(self, "converted", False):
-            if self.model.training:
-                raise RuntimeError("this model was converted to int8 inference (hip_convert): it cannot be trained; rebuild the QAT model")
+        if self.converted:
+            self._refuse_training()
             with torch.cuda.device(self.device):
                 return [a.dequant().contiguous() for a in self._maps_converted(x)]
         with torch.cuda.device(self.device):
@@ -782,10 +776,7 @@ class SSDRunner(FrostRunner):
             x = x.float()
         a, feats = self._trunk(x, training)
         obs, E = self._obs, self.E
-        ends, i = [], 0
-        for lname in ("layer1", "layer2", "layer3", "layer4", "layer5"):
-            i += len(getattr(self.model, lname))
-            ends.append(feats[i - 1])
+        ends = self._stage_ends(feats)
         sources = [ends[1], ends[2], ends[4]]
         for pw1, dw, pw2 in self.extras:
             a = E.conv(pw2, E.conv(dw, E.conv(pw1, a, training, obs), training, obs), training, obs)
