@@ -216,6 +216,10 @@ _PROTOS = {
     "frost_float_ssd_gather_f32": [P, I, I, L, L, P, P, P],
     "frost_float_ssd_scatter": [P, I, I, L, L, P, P, P],
     "frost_float_ssd_scatter_f32": [P, I, I, L, L, P, P, P],
+    "frost_ptq_site_words": [],
+    "frost_ptq_observe": [P, L, P, P, P],
+    "frost_ptq_observe_strided": [P, I, I, I, I, L, L, L, L, P, P, P],
+    "frost_ptq_coef": [P, I, P],
     "frost_infer_block_ok": [I, I, I, I, I, I, I, I, I, I],
     "frost_infer_block_w_ok": [I, I, I, I, I, I, I, I, I],
     "frost_infer_block_w": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P],

@@ -197,6 +197,15 @@ _SETTINGS = {
 }
 
 
+def _arena_bases(r):
+    """Storages the bound model's buffers are aliased onto: the runner's qrecord arena, and the calibration arena of a PTQ model (frostnet_amd.ptq)."""
+    out = {r.qa.t.untyped_storage().data_ptr()}
+    extra = getattr(r, "ptq_arena", None)
+    if extra is not None:
+        out.add(extra.untyped_storage().data_ptr())
+    return out
+
+
 class _FrostBase(_FlagNotify):
     def _make_layer(self, block, block_setting, width_mult, dilation=1):
         layers = list()
@@ -236,9 +245,9 @@ class _FrostBase(_FlagNotify):
         r = self.__dict__.get("_hip_runner")
         arena = getattr(getattr(r, "qa", None), "t", None)
         if arena is not None:
-            base = arena.untyped_storage().data_ptr()
+            bases = _arena_bases(r)
             for k, v in list(sd.items()):
-                if torch.is_tensor(v) and v.device == arena.device and v.untyped_storage().data_ptr() == base:
+                if torch.is_tensor(v) and v.device == arena.device and v.untyped_storage().data_ptr() in bases:
                     sd[k] = v.detach().clone()
         return sd
 
@@ -254,21 +263,26 @@ class _FrostBase(_FlagNotify):
         arena = getattr(getattr(r, "qa", None), "t", None)
         if arena is not None:
             import copy as _copy
-            base = arena.untyped_storage().data_ptr()
+            base = _arena_bases(r)
 
             def detach_aliases(mod):
                 new = _copy.copy(mod)                                   # shallow: parameters stay shared with the live module (deepcopy / pickle copy them)
-                new._buffers = {k: (v.detach().clone() if torch.is_tensor(v) and v.device == arena.device and v.untyped_storage().data_ptr() == base else v)
+                new._buffers = {k: (v.detach().clone() if torch.is_tensor(v) and v.device == arena.device and v.untyped_storage().data_ptr() in base else v)
                                 for k, v in mod._buffers.items()}
                 new._modules = {k: (detach_aliases(c) if c is not None else None) for k, c in mod._modules.items()}
                 return new
             d["_modules"] = {k: (detach_aliases(c) if c is not None else None) for k, c in self._modules.items()}
-            d["_buffers"] = {k: (v.detach().clone() if torch.is_tensor(v) and v.device == arena.device and v.untyped_storage().data_ptr() == base else v)
+            d["_buffers"] = {k: (v.detach().clone() if torch.is_tensor(v) and v.device == arena.device and v.untyped_storage().data_ptr() in base else v)
                              for k, v in self._buffers.items()}
         return d
 
     def _is_qat_prepared(self):
         return hasattr(self.conv1.conv[0], "weight_fake_quant")
+
+    def _is_ptq_prepared(self):
+        """fuse_model() + a PTQ qconfig + torch.quantization.prepare (frostnet_amd.ptq.ptq_prepare): observers on a fused float tree, no weight FakeQuantize."""
+        m = self.conv1.conv[0]
+        return hasattr(m, "activation_post_process") and not hasattr(m, "weight_fake_quant")
 
     def _flags_changed(self):
         r = self.__dict__.get("_hip_runner")
@@ -293,12 +307,13 @@ class _FrostBase(_FlagNotify):
             raise RuntimeError("nn.DataParallel replicas are not supported by the HIP path (replicas share one runner and its device-0 "
                                "pointers): data parallelism is one process per GPU -- frostnet_amd.parallel, `bench.py --gpus N`")
         qat = self._is_qat_prepared()
+        ptq = not qat and self._is_ptq_prepared()             # calibration (and, after hip_convert, int8 inference) of the post-training flow: frostnet_amd/ptq.py
         r = self.__dict__.get("_hip_runner")
         want = getattr(self, "float_precision", None)        # 'bf16' (default) | 'fp32': activation storage of the float (warm-up) path
-        if r is not None and not qat and want is not None and getattr(r, "precision", want) != want:
+        if r is not None and not qat and not ptq and want is not None and getattr(r, "precision", want) != want:
             r = None
-        if r is None or r.model is not self or r.is_qat != qat or not r.still_valid():
-            if qat and self.__dict__.get("_hip_converted", False):
+        if r is None or r.model is not self or r.is_qat != qat or getattr(r, "is_ptq", False) != ptq or not r.still_valid():
+            if (qat or ptq) and self.__dict__.get("_hip_converted", False):
                 # the converted state (int8 packs frozen at convert time) lived on the runner that is gone (parameters or buffers moved, or this is a
                 # deepcopy / unpickled copy of a converted model): converting again would move the weight observers a second time, silently running the
                 # fake-quant eval graph would be a different model.  Refuse -- on EVERY call: no runner is cached while the flag is set.
@@ -308,6 +323,9 @@ class _FrostBase(_FlagNotify):
             if qat:
                 from .runner import FrostRunner
                 r = FrostRunner(self)
+            elif ptq:
+                from .ptq import PtqRunner
+                r = PtqRunner(self)
             else:                                   # the float model: StatAssist warm-up training / float eval (float_train.py)
                 from .float_train import FloatRunner
                 r = FloatRunner(self)
@@ -319,6 +337,13 @@ class _FrostBase(_FlagNotify):
     def hip_convert(self):
         """Device counterpart of `torch.quantization.convert(model.eval(), inplace=True)` (Classification/evaluate.py:130): the QAT-prepared
         model on the HIP device switches to converted int8 inference semantics (frostnet_amd.runner.FrostRunner.convert)."""
+        if not self._is_qat_prepared() and hasattr(self, "conv1") and self._is_ptq_prepared():
+            # post-training flow: the calibrated observers' qparams (stock calculate_qparams on one host copy of the arena), then the same int8 engine
+            from .ptq import convert as _ptq_convert
+            self.eval()
+            self.__dict__["_hip_runner"] = _ptq_convert(self)
+            self.__dict__["_hip_converted"] = True
+            return self
         if not self._is_qat_prepared():
             raise RuntimeError("hip_convert needs the QAT-prepared model (fuse_model + prepare_qat), like torch.quantization.convert")
         self.eval()
@@ -417,6 +442,14 @@ for _q in (True, False):
 def create_model(name, pretrained=False, **kwargs):
     """timm-style entry point: `num_classes`/`pretrained` are accepted and ignored like the reference."""
     return MODEL_REGISTRY[name](**kwargs)
+
+
+def ptq_prepare(model, backend="qnnpack"):
+    """The reference's post-quantisation flow up to calibration: eval -> fuse -> get_default_qconfig(backend) -> torch.quantization.prepare
+    (frostnet_amd.ptq.ptq_prepare).  A CUDA tensor through the prepared model runs the calibration forward on the device; hip_convert() then
+    switches it to the converted int8 engine."""
+    from .ptq import ptq_prepare as _prep
+    return _prep(model, backend)
 
 
 def qat_prepare(model, version=0, backend="qnnpack"):

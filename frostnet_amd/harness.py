@@ -274,6 +274,27 @@ def val(val_loader, model, criterion, transform=None, graph=False):
     return _epoch(val_loader, model, criterion, None, 0, None, None, False, transform)
 
 
+def calibrate(loader, model, transform=None):
+    """The calibration loop of the post-training flow (the reference's "Post quantization examples": training images through the prepared model before
+    torch.quantization.convert): every batch of `loader` through the PTQ-prepared `model` (frostnet.ptq_prepare) in eval mode under torch.no_grad(), so that
+    its HistogramObservers see them -- on the device when the model lives there (frostnet_amd.ptq.PtqRunner: no host synchronisation per batch).  Batches are
+    `(input, ...)` tuples or, with a `transform` (a `ClassificationEvalTransform`), `(images uint8, sizes, ...)` as in `val`.  Returns the number of batches."""
+    model.eval()
+    dev = _device_of(model)
+    n = 0
+    with torch.no_grad():
+        for batch in loader:
+            if transform is None:
+                inp = (batch[0] if isinstance(batch, (tuple, list)) else batch).to(dev, non_blocking=True)
+            else:
+                inp = transform(batch[0].to(dev, non_blocking=True), batch[1].to(dev, non_blocking=True))
+            model(inp)
+            n += 1
+    if n == 0:
+        raise ValueError("empty loader")
+    return n
+
+
 def val_detector(loader, model, evaluator, top_k=200, conf_thresh=0.01, nms_thresh=0.45):
     """One validation pass of the detector: `model.eval()`, then for every (images, gt [N, G, 5], difficult [N, G], valid [N, G], sizes [N, 2] or None) of the
     loader (ssdlite.pad_targets / voc_eval.pad_difficult turn ragged targets into these) the detections [N, C, top_k, 5] go into `evaluator.update` -- from

@@ -507,8 +507,9 @@ class FrostRunner:
         sd = OrderedDict()
 
         def qparams(fq, shape):
-            sc = fq.scale.detach().float().reshape(-1)[:1].cpu()
-            zp = fq.zero_point.detach().reshape(-1)[:1].to(torch.int64).cpu()
+            scale, zero_point = self._site_qparams(fq)
+            sc = scale.detach().float().reshape(-1)[:1].cpu()
+            zp = zero_point.detach().reshape(-1)[:1].to(torch.int64).cpu()
             return sc.reshape(shape).clone(), zp.reshape(shape).clone()
         with torch.cuda.device(self.device):
             for name, mod in self.model.named_modules():
@@ -532,9 +533,13 @@ class FrostRunner:
                     sd[pre + "scale"], sd[pre + "zero_point"] = qparams(mod.activation_post_process, ())
                 elif isinstance(mod, torch.ao.quantization.QuantStub) and hasattr(mod, "activation_post_process"):
                     sd[pre + "scale"], sd[pre + "zero_point"] = qparams(mod.activation_post_process, (1,))
-                elif type(mod).__name__ == "FloatFunctional" and hasattr(mod.activation_post_process, "scale"):
+                elif type(mod).__name__ == "FloatFunctional" and self._site_qparams(mod.activation_post_process) is not None:
                     sd[pre + "scale"], sd[pre + "zero_point"] = qparams(mod.activation_post_process, ())
         return sd
+
+    def _site_qparams(self, fq):
+        """(scale, zero_point) tensors of an activation site's module, None for a site without any (an unobserved FloatFunctional)."""
+        return (fq.scale, fq.zero_point) if hasattr(fq, "scale") else None
 
     def _refuse_training(self):
         if self.model.training:

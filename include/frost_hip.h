@@ -484,6 +484,26 @@ int frost_float_ssd_gather_f32(const FrostSSDMap* maps, int nmaps, int n, int64_
 int frost_float_ssd_scatter(const FrostSSDMap* maps, int nmaps, int n, int64_t ldloc, int64_t ldconf, const float* dloc, const float* dconf, void* stream);
 int frost_float_ssd_scatter_f32(const FrostSSDMap* maps, int nmaps, int n, int64_t ldloc, int64_t ldconf, const float* dloc, const float* dconf, void* stream);
 
+/* ---- post-training quantisation: histogram calibration (csrc/frost_ptq.hip; CPU definition: frostnet_amd/ptq.py) ------------------------------
+ * One torch.ao.quantization.HistogramObserver.forward per call (2048 bins, upsample rate 16), all arithmetic fp32, bit-equal to stock torch on the CPU
+ * while every bin count of one call stays below 2^24.  `site` is FROST_PTQ_SITE_WORDS 32-bit words of device memory:
+ *   [0] min_val  [1] max_val  (+inf / -inf = no data yet)   [2] [3] batch min / max of the running call (kept at +inf / -inf between calls)
+ *   [FROST_PTQ_HDR .. +2048)  the histogram, fp32           [FROST_PTQ_HDR + 2048 .. +2048)  int32 counts of the running call (kept at zero between calls)
+ * Three launches on `stream`, no host synchronisation, no state outside `site`: batch range -> counts against the range the state and the batch decide
+ * (per-workgroup LDS histogram, integer atomics) -> one workgroup that combines them with the old histogram (same range: add; constant history: its mass into
+ * one bin; else the old histogram re-binned through 16 fine bins per bin) and stores the new state.  Capturable; a replay is the next batch.
+ * `nonfinite` (one int32): the number of NaN / inf values seen is added to it -- such values are outside the contract and are not counted into any bin.
+ * The strided entry reads a logical (n, c, h, w) tensor with element strides (the QuantStub's input). */
+#define FROST_PTQ_BINS 2048
+#define FROST_PTQ_HDR 16
+#define FROST_PTQ_SITE_WORDS (FROST_PTQ_HDR + 2 * FROST_PTQ_BINS)
+int frost_ptq_site_words(void);
+int frost_ptq_observe(const float* x, int64_t n, float* site, int32_t* nonfinite, void* stream);
+int frost_ptq_observe_strided(const float* x, int n, int c, int h, int w, int64_t sn, int64_t sc, int64_t sh, int64_t sw, float* site, int32_t* nonfinite,
+                              void* stream);
+/* coefficient rows (scale, bias) = (1, desc.beta) of fused float layers (Conv2d with the BatchNorm folded in: the conv bias travels in `beta`), whole table */
+int frost_ptq_coef(const FrostFDesc* descs, int nlayers, void* stream);
+
 typedef struct FrostOptTensor {
   float* p; float* g; float* exp_min; float* exp_max; float* coin; float* buf0; float* buf1; float* buf2;
   int64_t n; float weight_decay; float lr; int32_t first_step; int32_t pad;
