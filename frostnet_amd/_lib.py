@@ -90,7 +90,17 @@ class FrostOptHyper(C.Structure):
                 ("noise_scale", F), ("bc1", F), ("bc2", F), ("seed", C.c_uint64), ("offset", C.c_uint64)]
 
 
+class FrostEmaEntry(C.Structure):
+    """One (live tensor, shadow tensor) pair of the weight-EMA launch (a DEVICE table of these, include/frost_hip.h)."""
+    _fields_ = [("src", P), ("dst", P), ("n", C.c_int64), ("kind", C.c_int32), ("pad", C.c_int32)]
+
+
+EMA_LERP, EMA_COPY1, EMA_COPY4, EMA_COPY8, EMA_CHUNK, EMA_SMALL_ROWS = 0, 1, 2, 3, 4096, 256      # FROST_EMA_* of include/frost_hip.h
+
+
 _PROTOS = {
+    "frost_ema_entry_bytes": [],
+    "frost_ema_update": [P, I, P, I, P, P],
     "frost_abi_version": [],
     "frost_add_state_floats": [],
     "frost_ticket_words": [],
@@ -294,6 +304,8 @@ def load_library():
     if lib.frost_abi_version() != ABI_VERSION or lib.frost_ticket_words() != TICKET_WORDS or lib.frost_fin_desc_bytes() != C.sizeof(FrostFinDesc):
         raise RuntimeError(f"{LIB_PATH}: ABI mismatch (library abi {lib.frost_abi_version()} / ticket words {lib.frost_ticket_words()} / FrostFinDesc "
                            f"{lib.frost_fin_desc_bytes()} B, binding {ABI_VERSION} / {TICKET_WORDS} / {C.sizeof(FrostFinDesc)} B): rebuild with `python __graft_entry__.py`")
+    if lib.frost_ema_entry_bytes() != C.sizeof(FrostEmaEntry):
+        raise RuntimeError(f"{LIB_PATH}: FrostEmaEntry is {lib.frost_ema_entry_bytes()} B in the library, {C.sizeof(FrostEmaEntry)} B in the binding: rebuild with `python __graft_entry__.py`")
     _lib = lib
     return lib
 

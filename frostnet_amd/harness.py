@@ -225,7 +225,7 @@ def _device_of(model):
     return next(model.parameters()).device
 
 
-def _epoch(loader, model, criterion, optimizer, epoch, args, grad_sync, train_mode, transform=None):
+def _epoch(loader, model, criterion, optimizer, epoch, args, grad_sync, train_mode, transform=None, ema=None):
     dev = _device_of(model)
     sums, n = torch.zeros(3, dtype=torch.float64, device=dev), 0
     for i, batch in enumerate(loader):
@@ -240,6 +240,8 @@ def _epoch(loader, model, criterion, optimizer, epoch, args, grad_sync, train_mo
             if args is not None and getattr(args, "lrsch", "cos_lr") == "cos_lr" and hasattr(args, "dataset_len"):
                 adjust_learning_rate_cosine(optimizer, epoch, i, args.dataset_len, args)
             loss, out = train_one_iter(model, criterion, optimizer, inp, target, grad_sync)
+            if ema is not None:
+                ema.update(model)
         else:
             with torch.no_grad():
                 out = model(inp)
@@ -253,15 +255,16 @@ def _epoch(loader, model, criterion, optimizer, epoch, args, grad_sync, train_mo
     return loss, a1, a5
 
 
-def train(train_loader, model, criterion, optimizer, epoch, total_ep=None, args=None, grad_sync=None, transform=None, graph=False):
+def train(train_loader, model, criterion, optimizer, epoch, total_ep=None, args=None, grad_sync=None, transform=None, graph=False, ema=None):
     """One training epoch (helper_functions.py:99-163): returns (mean loss, mean top-1, mean top-5) over the iterations.  With a `transform` (a
     `ClassificationAugmentation`) the loader yields (images uint8, sizes, target) in `pad_images`' format and the transform turns them into the model's input on the device.
     `graph`: True drives a `GraphedStep` made for this call (the iteration replayed as one hipGraph, loss and accuracies summed by the loss kernel into an `EpochMeter`);
-    pass a `GraphedStep` of your own so that the capture survives across epochs."""
+    pass a `GraphedStep` of your own so that the capture survives across epochs.  `ema` (a `frostnet_amd.ema.ModelEma`): updated after every optimizer step, inside the
+    captured iteration when there is one; validate `ema.module`."""
     model.train()
     if graph is not False and graph is not None:
-        return _epoch_graphed(train_loader, _graphed(graph, model, criterion, optimizer, transform, grad_sync), epoch, args, True)
-    return _epoch(train_loader, model, criterion, optimizer, epoch, args, grad_sync, True, transform)
+        return _epoch_graphed(train_loader, _graphed(graph, model, criterion, optimizer, transform, grad_sync, ema), epoch, args, True)
+    return _epoch(train_loader, model, criterion, optimizer, epoch, args, grad_sync, True, transform, ema)
 
 
 def val(val_loader, model, criterion, transform=None, graph=False):
@@ -334,7 +337,7 @@ def _is_plain_ce(criterion):
 
 class _Captured:
     """One captured input signature of a GraphedStep: static inputs, their staging buffers, the graph(s) and what they were captured against."""
-    __slots__ = ("statics", "staging", "graph", "seg", "plan", "runner", "training", "logits", "staged", "free", "rows", "dp_in")
+    __slots__ = ("statics", "staging", "graph", "seg", "plan", "runner", "training", "logits", "staged", "free", "rows", "dp_in", "ema_plan", "ema_id")
 
 
 class GraphedStep:
@@ -353,6 +356,11 @@ class GraphedStep:
     augmentation and dropout stream positions (device words).  The step is captured AGAIN, never replayed stale, when the model's runner is no longer valid, when the
     optimizer's plan changed (`load_state_dict`, `add_param_group`) or when `model.training` differs from the capture.
 
+    `ema` (a `frostnet_amd.ema.ModelEma`): the weight average moves after every optimizer step -- eagerly `ema.update(model)`, on the captured path `ema.prepare_step()` next to
+    the optimizer's in front of capture and replay (w = 1 - decay_t is a device word outside the graph, the pointer table is revalidated there) and `ema.launch(plan)`
+    recorded right behind `optimizer.launch(plan)`.  The shadow's runner is bound during the eager warm-up calls so that its table settles before the capture; the step is
+    captured again when `ema.plan_id` changed.  Data parallel: the launch follows the optimizer's on every rank, no collective (equal parameters, equal shadows).
+
     Data parallel (`group` given, or a default process group of more than one rank): the body is `parallel.SegmentedStep` (capture / replay / finish, then the optimizer
     launch); collectives are never captured.  A float model (StatAssist warm-up: `FloatRunner`, `FloatSSDRunner`), a CPU model and an optimizer without `prepare_step` /
     `launch` run the same iteration eagerly (the float step measured slower replayed than eager) -- still with the fused metrics.
@@ -360,9 +368,12 @@ class GraphedStep:
     Classifier metrics go to `meter` (an `EpochMeter`: the criterion's own when it is a `CrossEntropyWithMetrics`; a plain cross-entropy criterion is replaced by one); the
     logits of the last iteration are `logits`.  Detector: `record` = three device doubles {sum loss_l, sum loss_c, batches}, `loss_terms` = the last (loss_l, loss_c)."""
 
-    def __init__(self, model, criterion, optimizer=None, transform=None, nbuckets=4, group=None, eager_warmup=2):
+    def __init__(self, model, criterion, optimizer=None, transform=None, nbuckets=4, group=None, eager_warmup=2, ema=None):
         from .ssdlite import MultiBoxLoss
         self.model, self.optimizer, self.transform, self.nbuckets, self.group = model, optimizer, transform, nbuckets, group
+        if ema is not None and optimizer is None:
+            raise ValueError("GraphedStep(ema=...) averages the weights after the optimizer step: it needs an optimizer")
+        self.ema = ema
         self.eager_warmup = max(int(eager_warmup), 1 if optimizer is not None else 0)          # the optimizer's table is built from the gradients of a first eager step
         self.device = dev = _device_of(model)
         self.detector = isinstance(criterion, MultiBoxLoss)
@@ -476,6 +487,7 @@ class GraphedStep:
         self.loss.copy_(self._seg_eager.run_eager(x, target))
         self._seg_eager.finish()
         self.optimizer.step()
+        self._ema_eager()
         self.logits = None
         return self.loss
 
@@ -495,7 +507,13 @@ class GraphedStep:
         self.logits = self._forward_backward(batch)
         if self.optimizer is not None:
             self.optimizer.step()
+            self._ema_eager()
         return self.loss
+
+    def _ema_eager(self):
+        if self.ema is not None:
+            self.ema.bind_shadow()            # (once: the shadow's runner re-aliases its buffers; later calls find it)
+            self.ema.update(self.model)
 
     # ---- input copy ----
     def _load(self, g, batch):
@@ -520,13 +538,14 @@ class GraphedStep:
             g.free.record(cur)
 
     # ---- capture / replay ----
-    def _capture(self, sig, batch, plan):
+    def _capture(self, sig, batch, plan, ema_plan=None):
         dev = self.device
         g = _Captured()
         g.statics = [torch.empty(t.shape, dtype=t.dtype, device=dev) for t in batch]
         g.staging = [None if t.is_cuda else torch.empty(t.shape, dtype=t.dtype, device=dev) for t in batch]
         g.staged, g.free, g.graph, g.seg, g.logits, g.dp_in, g.rows = torch.cuda.Event(), None, None, None, None, None, batch[0].size(0)
         g.runner, g.training, g.plan = self.model.hip_runner(), self.model.training, plan
+        g.ema_plan, g.ema_id = ema_plan, None if ema_plan is None else ema_plan["id"]
         self._load(g, batch)
         import torch.distributed as dist
         with torch.cuda.device(dev):
@@ -545,6 +564,8 @@ class GraphedStep:
                         g.logits = self._forward_backward(tuple(g.statics))
                         if self.optimizer is not None:
                             self.optimizer.launch(plan)
+                        if ema_plan is not None:
+                            self.ema.launch(ema_plan)
                 torch.cuda.current_stream(dev).wait_stream(side)
         self.captures += 1
         self._graphs[sig] = g
@@ -560,6 +581,8 @@ class GraphedStep:
             g.seg.replay()
             g.seg.finish()
             self.optimizer.launch(g.plan)
+            if g.ema_plan is not None:
+                self.ema.launch(g.ema_plan)
             self.loss.copy_(g.seg.loss)
         else:
             g.graph.replay()
@@ -592,14 +615,17 @@ class GraphedStep:
                     self._graphs.clear()
                 return self._eager(batch)
             plan = self.optimizer.prepare_step() if self.optimizer is not None else None
-            g = self._capture(sig, batch, plan)
+            ema_plan = self.ema.prepare_step(self.model) if self.ema is not None else None
+            g = self._capture(sig, batch, plan, ema_plan)
             return self._replay(g, captured_now=True)
         self._load(g, batch)
         if self.optimizer is not None:
             plan = self.optimizer.prepare_step()
-            if plan is not g.plan:                    # load_state_dict / add_param_group: the captured launch reads the old table
+            ema_plan = self.ema.prepare_step(self.model) if self.ema is not None else None
+            # load_state_dict / add_param_group: the captured launch reads the old table; an EMA plan rebuilt for other entries likewise
+            if plan is not g.plan or (ema_plan is not None and (ema_plan is not g.ema_plan or ema_plan["id"] != g.ema_id)):
                 del self._graphs[sig]
-                return self._replay(self._capture(sig, batch, plan), captured_now=True)
+                return self._replay(self._capture(sig, batch, plan, ema_plan), captured_now=True)
         return self._replay(g)
 
     __call__ = step
@@ -618,15 +644,17 @@ class GraphedStep:
         return sl / nb, sc / nb
 
 
-def _graphed(graph, model, criterion, optimizer, transform, grad_sync):
+def _graphed(graph, model, criterion, optimizer, transform, grad_sync, ema=None):
     if grad_sync is not None:
         raise ValueError("graph=True exchanges the gradients itself (parallel.SegmentedStep between the graph's segments): pass a GraphedStep(..., group=...) "
                          "instead of grad_sync")
     if isinstance(graph, GraphedStep):
         if graph.model is not model or graph.optimizer is not optimizer or graph.transform is not transform:
             raise ValueError("graph=<GraphedStep>: it was built for another model, optimizer or transform")
+        if ema is not None and graph.ema is not ema:
+            raise ValueError("graph=<GraphedStep>: it was built without this ema (GraphedStep(..., ema=ema))")
         return graph
-    return GraphedStep(model, criterion, optimizer, transform)
+    return GraphedStep(model, criterion, optimizer, transform, ema=ema)
 
 
 def _epoch_graphed(loader, step, epoch, args, train_mode):
@@ -642,17 +670,17 @@ def _epoch_graphed(loader, step, epoch, args, train_mode):
     return step.read_record()                      # the epoch's single device -> host read
 
 
-def train_detector(loader, model, criterion, optimizer, start_iter, max_iter, lr, gamma, lr_steps, transform=None, graph=False):
+def train_detector(loader, model, criterion, optimizer, start_iter, max_iter, lr, gamma, lr_steps, transform=None, graph=False, ema=None):
     """The detector's training loop (Object_Detection/qtrainval.py:259-304), driven by the iteration count: iterations start_iter .. max_iter - 1, the learning rate set
     to lr * gamma^step_index at every entry of `lr_steps` (:270-272, adjust_learning_rate :336-344), the loader restarted whenever it is exhausted.  The loader yields
     (images, boxes, valid) (ssdlite.pad_targets' format), or (images uint8, sizes, boxes, valid) for a `transform` (an `SSDAugmentation`, on the device in front of the
     model).  `graph`: False = eager launches, True = a `GraphedStep` made here, or a `GraphedStep` of the caller's so that the capture survives across calls.  Returns the
-    mean (loss_l, loss_c) over the iterations from one host read."""
+    mean (loss_l, loss_c) over the iterations from one host read.  `ema`: as in `train`."""
     model.train()
     if isinstance(graph, GraphedStep):
-        step = _graphed(graph, model, criterion, optimizer, transform, None)
+        step = _graphed(graph, model, criterion, optimizer, transform, None, ema)
     else:
-        step = GraphedStep(model, criterion, optimizer, transform)
+        step = GraphedStep(model, criterion, optimizer, transform, ema=ema)
         step.capture = bool(graph)
     if not step.detector:
         raise ValueError("train_detector: criterion must be a ssdlite.MultiBoxLoss")
@@ -678,9 +706,13 @@ def train_detector(loader, model, criterion, optimizer, start_iter, max_iter, lr
     return step.read_record()
 
 
-def checkpoint_state(model, optimizer, epoch, **scalars):
-    """The dictionary Classification/train.py:208-218 saves every epoch (same keys; `scalars` = lossTr, lossVal, acc1Tr, ... , lr, Max_name ...)."""
+def checkpoint_state(model, optimizer, epoch, ema=None, **scalars):
+    """The dictionary Classification/train.py:208-218 saves every epoch (same keys; `scalars` = lossTr, lossVal, acc1Tr, ... , lr, Max_name ...).  With `ema` (a
+    `ModelEma`) also `state_dict_ema` -- the shadow's state_dict, the key timm writes and `frostnet_features` prefers on ingest -- and `ema_updates`."""
     state = {"epoch": epoch + 1, "arch": str(type(model).__name__), "state_dict": model.state_dict(), "optimizer": optimizer.state_dict()}
+    if ema is not None:
+        state["state_dict_ema"] = ema.module.state_dict()
+        state["ema_updates"] = ema.updates
     state.update(scalars)
     runner = getattr(model, "_hip_runner", None)
     if runner is not None and hasattr(runner, "rng_state"):
@@ -692,11 +724,16 @@ def save_checkpoint(state, filenameCheckpoint="checkpoint.pth.tar"):
     torch.save(state, filenameCheckpoint)
 
 
-def load_checkpoint(model, optimizer, filenameCheckpoint="checkpoint.pth.tar", map_location=None):
-    """Resume: parameters / buffers (BN statistics, observer ranges, qparams), optimizer state (GradBoost statistics, step count = Philox offset)
-    and the dropout stream.  Returns the checkpoint dictionary (epoch, best accuracies ...)."""
+def load_checkpoint(model, optimizer, filenameCheckpoint="checkpoint.pth.tar", map_location=None, ema=None):
+    """Resume: parameters / buffers (BN statistics, observer ranges, qparams), optimizer state (GradBoost statistics, step count = Philox offset),
+    the dropout stream and, with `ema`, the weight average and its update count.  Returns the checkpoint dictionary (epoch, best accuracies ...)."""
     ck = torch.load(filenameCheckpoint, map_location=map_location, weights_only=False)
     model.load_state_dict(ck["state_dict"])
+    if ema is not None:
+        if "state_dict_ema" not in ck:
+            raise KeyError(f"{filenameCheckpoint} holds no weight average (state_dict_ema)")
+        ema.module.load_state_dict(ck["state_dict_ema"])
+        ema.updates = int(ck.get("ema_updates", 0))
     if optimizer is not None and "optimizer" in ck:
         optimizer.load_state_dict(ck["optimizer"])
     if "hip_rng" in ck and hasattr(model, "hip_runner"):

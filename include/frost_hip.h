@@ -524,6 +524,26 @@ typedef struct FrostOptHyper {
 int frost_gradboost_step(const FrostOptTensor* table, int ntensors, int64_t max_n, const FrostOptHyper* hyper,
                          const float* noise, const float* coin, const int64_t* prefix, void* stream);
 
+/* ---- weight EMA of a module tree (timm ModelEmaV3), one multi-tensor launch (additive export, ABI 5) ----------------------------------------
+ * Per entry dst <- lerp(dst, src, w) on fp32 words, dst = fmaf(w, src - dst, dst) with w = 1 - decay read from ONE device word (`weight`, outside any
+ * captured graph: a replay sees this step's value), or a raw copy of 1-, 4- or 8-byte elements.  A src word that is not finite is copied, not averaged.
+ * table and wgmap are DEVICE memory.  wgmap = int32 x 4 rows; the first nwg rows are one workgroup each:
+ *   {0, entry, chunk, 0}          units [chunk * FROST_EMA_CHUNK, ...) of a large entry (a unit = one element; an 8-byte element is two 4-byte units)
+ *   {1, first row, rows, units}   rows <= FROST_EMA_SMALL_ROWS small entries, listed from row `first row` (>= nwg) on as {entry, first unit of that entry
+ *                                 within the workgroup's slice, 0, 0} with strictly increasing prefixes; `units` = the slice's total
+ * src / dst of the 4- and 8-byte kinds need 4-byte alignment only; 16-byte vector accesses are used where both sides share their offset mod 16. */
+#define FROST_EMA_LERP 0
+#define FROST_EMA_COPY1 1
+#define FROST_EMA_COPY4 2
+#define FROST_EMA_COPY8 3
+#define FROST_EMA_CHUNK 4096
+#define FROST_EMA_SMALL_ROWS 256
+typedef struct FrostEmaEntry {
+  const void* src; void* dst; int64_t n; int32_t kind; int32_t pad;
+} FrostEmaEntry;
+int frost_ema_entry_bytes(void);   /* == sizeof(FrostEmaEntry) of the library that was loaded */
+int frost_ema_update(const FrostEmaEntry* table, int nentries, const int32_t* wgmap, int nwg, const float* weight, void* stream);
+
 /* ---- statistics pass with the finalize folded into its tail --------------------------------------------------------------------------
  * frost_pw_conv_fwd / frost_dw_conv_fwd (mode 0) + frost_conv_finalize in ONE launch: the last workgroup to finish (device-scope ticket)
  * turns the integer statistics into the BN coefficients / running statistics / activation qparams, so a conv forward is two launches
