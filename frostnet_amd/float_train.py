@@ -23,13 +23,11 @@ import torch
 
 from . import _lib as L
 from ._lib import call, ptr, stream
+from .topology import (FEATURE_TAPS, SSD_TAPS, FloatLayer, GradArena, act_code, bind_block, bind_detector, bind_trunk, conv_out_hw, model_signature,
+                       plan_block, plan_tree, round_up)
 
 STATS, EMIT, BRED, BDC = 0, 1, 2, 3
 DESC_BYTES = C.sizeof(L.FrostFDesc)
-
-
-def round_up(a, b):
-    return (a + b - 1) // b * b
 
 
 class FAct:
@@ -55,33 +53,18 @@ _WGRAD_SIDE = os.environ.get("FROST_FLOAT_WGRAD_SIDE", "1") != "0"      # weight
 _LAZY_EMIT = os.environ.get("FROST_FLOAT_LAZY_EMIT", "1") != "0"        # training: conv1's activation is never written -- the depthwise kernels apply BN + ReLU to its kept conv output on load (A/B knob)
 
 
-def _act_code(mod):
-    """Activation code of the float kernels' `relu` argument (csrc/frost_float.hip: 0 none, 1 ReLU, 2 hard-swish) for an activated layer module."""
-    from .frostnet import ConvBNHswish
-    return 2 if isinstance(mod, ConvBNHswish) else 1
-
-
-class _FLayer:
+class _FLayer(FloatLayer):
     def __init__(self, name, seq, relu, dev, stem=False, fp32=False):
         conv, bn = seq[0], seq[1]
         if not isinstance(conv, torch.nn.Conv2d) or not isinstance(bn, torch.nn.BatchNorm2d):
             raise RuntimeError("the float device path expects the un-fused float model (Conv2d + BatchNorm2d per layer)")
-        self.name, self.conv, self.bn, self.relu = name, conv, bn, relu
-        self.cout, self.cin_g, self.k = conv.out_channels, conv.in_channels // conv.groups, conv.kernel_size[0]
-        self.stride = conv.stride[0]
-        self.kind = 2 if stem else (1 if conv.groups > 1 else 0)
-        self.cpad = round_up(self.cout, 16)
-        self.pack_t, self.kpad_t, self.fp32 = None, 0, fp32
-        kq = 16 if fp32 else 32                 # elements per 64-byte K step of the MFMA A-fragment pack
-        if self.kind == 1:
-            self.kpad = 0
-            self.pack = torch.zeros(self.k * self.k * self.cpad, dtype=torch.float32, device=dev)
-        else:
-            self.kpad = 64 if stem else round_up(self.cin_g, kq)
-            self.pack = torch.zeros((self.cpad // 16) * (self.kpad // kq) * 1024, dtype=torch.uint8, device=dev)
-            if self.kind == 0:
-                self.kpad_t = round_up(self.cout, kq)
-                self.pack_t = torch.zeros((round_up(self.cin_g, 16) // 16) * (self.kpad_t // kq) * 1024, dtype=torch.uint8, device=dev)
+        kq = 16 if fp32 else 32
+        super().__init__(conv, dev, stem, kq)
+        self.name, self.bn, self.relu, self.fp32 = name, bn, relu, fp32
+        self.pack_t, self.kpad_t = None, 0
+        if self.kind == 0:               # the transposed pack of the data gradient's GEMM
+            self.kpad_t = round_up(self.cout, kq)
+            self.pack_t = torch.zeros(self.pack_bytes(self.cin_g, self.kpad_t, kq), dtype=torch.uint8, device=dev)
         self.stat = torch.zeros(8 * 4 * self.cpad, dtype=torch.float64, device=dev)       # FST_SLOTS copies of [sum, sum of squares, S1, S2]
         self.coef = torch.zeros(8 * self.cpad, dtype=torch.float32, device=dev)
         self.x = None          # saved input of the last recorded forward
@@ -127,7 +110,7 @@ class _FloatFeatFunction(torch.autograd.Function):
         return None, None, None
 
 
-class FloatRunner:
+class FloatRunner(GradArena):
     """Binds a float FrostNet (classification model or features backbone) to the float HIP kernels."""
 
     def __init__(self, model, precision=None):
@@ -141,16 +124,10 @@ class FloatRunner:
         self.model, self.device = model, params[0].device
         self._bind_params(params)
         self.layers = []
-        self.stem = self._add("conv1", model.conv1.conv, _act_code(model.conv1), stem=True)
-        self.blocks, self.stage_ends = [], []
-        for lname in ("layer1", "layer2", "layer3", "layer4", "layer5"):
-            for bi, blk in enumerate(getattr(model, lname)):
-                self.blocks.append(self._bind_block(f"{lname}.{bi}", blk))
-            self.stage_ends.append(len(self.blocks) - 1)
-        self.last = self._add("last_layer", model.last_layer.conv, _act_code(model.last_layer)) if hasattr(model, "last_layer") else None
-        self.fc = model.classifier[2] if hasattr(model, "classifier") else None
-        self.drop_rate = float(model.classifier[1].p) if self.fc is not None else 0.0
-        self._bind_extra()
+        plan = plan_tree(model)
+        self.stem, self.blocks, self.last = bind_trunk(plan, self._add)
+        self.stage_ends, self.fc, self.drop_rate = plan.stage_ends, plan.classifier, plan.drop_rate
+        self.extras, self.heads = bind_detector(plan, self._add)
         self._finish()
         self._stem_tmp = torch.zeros(self.stem.cout * 64, dtype=torch.float32, device=self.device)
 
@@ -180,32 +157,9 @@ class FloatRunner:
         r.model, r.device = block, next(block.parameters()).device
         r._bind_params(list(block.parameters()))
         r.layers, r.stem, r.last, r.fc = [], None, None, None
-        r.blocks = [r._bind_block("B", block)]
+        r.blocks = [bind_block(plan_block("B", block), r._add)]
         r._finish()
         return r
-
-    def _bind_params(self, params):
-        self._params = params
-        self.grad_arena = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=self.device)
-        self._grad_views, self._gv, off = [], {}, 0
-        for p in params:
-            v = self.grad_arena[off: off + p.numel()].view_as(p)
-            self._grad_views.append(v)
-            self._gv[id(p)] = v
-            off += p.numel()
-
-    def _bind_extra(self):
-        """Layers a subclass binds behind the backbone (FloatSSDRunner: the SSDLite extras and heads); none for the classifier / features backbone."""
-
-    def _bind_block(self, pre, blk):
-        ent = dict(blk=blk, squeeze=None, conv1=None)
-        if blk.expand_ratio != 1:
-            if blk.block_type == "CAS":
-                ent["squeeze"] = self._add(pre + ".squeeze_conv", blk.squeeze_conv.conv, _act_code(blk.squeeze_conv))
-            ent["conv1"] = self._add(pre + ".conv1", blk.conv1.conv, _act_code(blk.conv1))
-        ent["conv2"] = self._add(pre + ".conv2", blk.conv2.conv, _act_code(blk.conv2))
-        ent["reduce"] = self._add(pre + ".reduce_conv", blk.reduce_conv.conv, 0)
-        return ent
 
     def _finish(self):
         arr = (L.FrostFDesc * len(self.layers))()
@@ -214,8 +168,7 @@ class FloatRunner:
         self._table = L.struct_to_tensor(arr, self.device)
         for i, l in enumerate(self.layers):
             l.desc_ptr = C.c_void_p(self._table.data_ptr() + i * DESC_BYTES)
-        m = self.model
-        self._sig = tuple(p.data_ptr() for p in m.parameters()) + tuple(b.data_ptr() for b in m.buffers())
+        self._sig = model_signature(self.model)
         self.on_grads_ready = None      # data-parallel hook: called once when the backward has written every gradient
 
     def to_act(self, x):
@@ -236,8 +189,8 @@ class FloatRunner:
         self._end_backward()
         return yf, dx.float().contiguous()
 
-    def _add(self, name, seq, relu, stem=False):
-        l = _FLayer(name, seq, relu, self.device, stem, self.fp32)
+    def _add(self, name, wrapper, kind):
+        l = _FLayer(name, wrapper.conv, act_code(wrapper), self.device, kind == "stem", self.fp32)
         self.layers.append(l)
         return l
 
@@ -252,25 +205,13 @@ class FloatRunner:
         set_rng_state(self, state)
 
     def still_valid(self):
-        m = self.model
-        return self._sig == tuple(p.data_ptr() for p in m.parameters()) + tuple(b.data_ptr() for b in m.buffers())
+        return self._sig == model_signature(self.model)
 
     def enable_data_parallel(self, nbuckets=1, group=None):
         """Data-parallel warm-up: the same one exchange step as the fake-quant path (frostnet_amd.parallel.GradSync over the flat
         gradient arena); the float backward hands the whole arena over when it ends, `grad_sync.finish()` waits and averages."""
-        from .parallel import GradSync
-        offs, off = [], 0
-        for p in self._params:
-            offs.append(off)
-            off += p.numel()
-        self.grad_sync = GradSync(self.grad_arena, offs, nbuckets, group)
         self.on_grads_ready = lambda: self.grad_sync.ready(0)
-        return self.grad_sync
-
-    def bind_grads(self):
-        for p, v in zip(self._params, self._grad_views):
-            if p.grad is None or p.grad.data_ptr() != v.data_ptr():
-                p.grad = v
+        return self._attach_grad_sync(nbuckets, group)
 
     def _new(self, n, h, w, c):
         return FAct(torch.empty(n * h * w * c + 64, dtype=self._adt, device=self.device), n, h, w, c)
@@ -280,11 +221,7 @@ class FloatRunner:
         """Conv -> BN -> [ReLU] (frostnet.py:14-60).  `out`/`ldy`: write into a slice of a wider buffer (the cat).
         lazy (training, kept conv output): no emit pass -- the returned activation carries the conv output and `src`, its only consumer (the depthwise layer)
         applies BN + ReLU on load (frost_float_dw_src / frost_float_dw_wgrad_src)."""
-        if l.kind == 1:
-            pad = (l.k - 1) // 2
-            ho, wo = (a.h + 2 * pad - l.k) // l.stride + 1, (a.w + 2 * pad - l.k) // l.stride + 1
-        else:
-            ho, wo = a.h, a.w
+        ho, wo = conv_out_hw(a.h, a.w, l.k, l.stride) if l.kind == 1 else (a.h, a.w)
         lazy = bool(lazy and out is None and training and _KEEP_CONV)
         y = self._new(a.n, ho, wo, l.cout) if (out is None and not lazy) else None
         npix_o = a.n * ho * wo
@@ -363,8 +300,7 @@ class FloatRunner:
         call("frost_float_weight_prep", ptr(self._table), len(self.layers), stream())
         if not training:
             call("frost_float_bn_eval", ptr(self._table), len(self.layers), stream())
-        ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-        col = self._new(n, ho, wo, 64)
+        col = self._new(n, *conv_out_hw(h, w, 3, 2), 64)
         call(self._fn["im2col"], ptr(x), n, h, w, x.stride(0), x.stride(1), x.stride(2), x.stride(3), ptr(col.buf), stream())
         a = self._conv(self.stem, col, training, record)
         outs = []
@@ -403,18 +339,13 @@ class FloatRunner:
 
     def _features_impl(self, x, record):
         _, outs = self._trunk(x, self.model.training, record)
-        e = self.stage_ends
-        return [outs[e[0]], outs[e[1]], outs[e[2]], outs[e[4]]]          # x4 is skipped (frostnet_features.py:350)
+        return [outs[self.stage_ends[i]] for i in FEATURE_TAPS]
 
     # ------------------------------------------------------------------------------------------ backward
     def _conv_bwd(self, l, gy, ldg, need_dx):
         """gy: device pointer (c_void_p) of the bf16 output gradient, rows of ldg elements.  Returns dx (FAct) or None."""
         a = l.x
-        if l.kind == 1:
-            pad = (l.k - 1) // 2
-            ho, wo = (a.h + 2 * pad - l.k) // l.stride + 1, (a.w + 2 * pad - l.k) // l.stride + 1
-        else:
-            ho, wo = a.h, a.w
+        ho, wo = conv_out_hw(a.h, a.w, l.k, l.stride) if l.kind == 1 else (a.h, a.w)
         npix_o = a.n * ho * wo
         dc = torch.empty(npix_o * l.cout + 64, dtype=self._adt, device=self.device)
         gw = self._gv[id(l.conv.weight)]
@@ -559,9 +490,8 @@ class FloatRunner:
 
     def _backward_features(self, acts, grads):
         self._begin_backward()
-        e = self.stage_ends
         taps = {}
-        for bi, a, gr in zip((e[0], e[1], e[2], e[4]), acts, grads):
+        for bi, a, gr in zip((self.stage_ends[i] for i in FEATURE_TAPS), acts, grads):
             if gr is None:
                 continue
             t = self._new(a.n, a.h, a.w, a.c)
@@ -628,14 +558,9 @@ class FloatSSDRunner(FloatRunner):
         self._fn["ssd_gather"] = "frost_float_ssd_gather" + sfx
         self._fn["ssd_scatter"] = "frost_float_ssd_scatter" + sfx
 
-    def _bind_extra(self):
-        m = self.model
-        self.anchors, self.num_classes = list(m.ANCHORS), int(m.num_classes)
-        self.extras = [(self._add(f"extras.{i}.pw1", e.pw1.conv, _act_code(e.pw1)), self._add(f"extras.{i}.dw", e.dw.conv, _act_code(e.dw)),
-                        self._add(f"extras.{i}.pw2", e.pw2.conv, _act_code(e.pw2))) for i, e in enumerate(m.extras)]
-        self.heads = [(self._add(f"loc.{i}.dw", l.dw.conv, _act_code(l.dw)), self._add(f"loc.{i}.pw", l.pw.conv, 0),
-                       self._add(f"conf.{i}.dw", c.dw.conv, _act_code(c.dw)), self._add(f"conf.{i}.pw", c.pw.conv, 0))
-                      for i, (l, c) in enumerate(zip(m.loc, m.conf))]
+    def __init__(self, model, precision=None):
+        super().__init__(model, precision)
+        self.anchors, self.num_classes = list(model.ANCHORS), int(model.num_classes)
 
     def _check_train_input(self, x):
         """torch BatchNorm2d refuses a training forward with one value per channel; here the 1x1 tail maps would otherwise be normalised with var = 0."""
@@ -666,8 +591,7 @@ class FloatSSDRunner(FloatRunner):
         if training:
             self._check_train_input(x)
         a, outs = self._trunk(x, training, record)
-        e = self.stage_ends
-        sources = [outs[e[1]], outs[e[2]], outs[e[4]]]
+        sources = [outs[self.stage_ends[i]] for i in SSD_TAPS]
         for pw1, dw, pw2 in self.extras:           # pw1 -> dw like conv1 -> conv2 of a block: the depthwise layer applies pw1's BN + ReLU on load
             t = self._conv(pw1, a, training, record, lazy=_LAZY_EMIT)
             a = self._conv(pw2, self._conv(dw, t, training, record), training, record)
@@ -733,5 +657,4 @@ class FloatSSDRunner(FloatRunner):
             d = self._conv_bwd(dw, ptr(d.buf), d.c, True)
             d = self._conv_bwd(pw1, ptr(d.buf), d.c, True)
             g = self._sum(srcg[i + 2], d)
-        e = self.stage_ends
-        self._trunk_bwd(None, {e[1]: srcg[0], e[2]: srcg[1], e[4]: g})
+        self._trunk_bwd(None, dict(zip((self.stage_ends[i] for i in SSD_TAPS), (srcg[0], srcg[1], g))))

@@ -17,10 +17,7 @@ import torch
 
 from . import _lib as L
 from ._lib import call, ptr, stream
-
-
-def round_up(a, b):
-    return (a + b - 1) // b * b
+from .topology import FEATURE_TAPS, SSD_TAPS, FloatLayer, act_code, bind_detector, bind_trunk, conv_out_hw, plan_tree
 
 
 # Whole-bottleneck fused kernel (csrc/frost_iblock.hip): "1" = every bottleneck the kernel takes (tile from pick_tile), "0" = layer-by-layer launches, "auto"
@@ -35,8 +32,7 @@ TILE_CANDIDATES = ((0, 0), (-1, 0), (7, 14), (8, 16), (16, 16), (7, 7), (8, 8), 
 
 
 def candidate_tiles(lib, h, w, cin, r, cexp, cout, k, stride):
-    pad = (k - 1) // 2
-    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    ho, wo = conv_out_hw(h, w, k, stride)
     out = []
     for th, tw in TILE_CANDIDATES:
         th, tw = (ho, wo) if th == 0 else (((ho + 1) // 2, wo) if th < 0 else (min(th, ho), min(tw, wo)))
@@ -49,8 +45,7 @@ def pick_tile(lib, h, w, cin, r, cexp, cout, k, stride):
     """Spatial output tile (th, tw) of one workgroup of frost_infer_block by a cost model (FROST_INFER_FUSED=1; the default mode "auto" measures the candidates
     instead, Bf16Inference._block): region pixels conv1 computes per output pixel plus a fixed per-tile cost, mildly weighted by the residency the tile's LDS
     footprint allows.  None: the fused kernel does not take this geometry."""
-    pad = (k - 1) // 2
-    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    ho, wo = conv_out_hw(h, w, k, stride)
     cands = [(ho, wo), ((ho + 1) // 2, wo), (7, 14), (8, 16), (7, 7), (8, 8), (4, 8), (4, 4)]
     if os.environ.get("FROST_IB_TILE"):
         cands = [tuple(int(v) for v in os.environ["FROST_IB_TILE"].split(","))] + cands[-1:]
@@ -71,24 +66,15 @@ def pick_tile(lib, h, w, cin, r, cexp, cout, k, stride):
     return None if best is None else (best[1], best[2])
 
 
-class _ILayer:
-    __slots__ = ("kind", "k", "stride", "relu", "cout", "cin_g", "cpad", "kpad", "pack", "biasf", "conv", "bn")
+class _ILayer(FloatLayer):
+    __slots__ = ("relu", "biasf", "bn")
 
     def __init__(self, seq, relu, dev, stem=False):
         conv, bn = seq[0], seq[1]
         if not isinstance(conv, torch.nn.Conv2d) or not isinstance(bn, torch.nn.BatchNorm2d):
             raise RuntimeError("bf16 inference expects the un-fused float model (Conv2d + BatchNorm2d per layer)")
-        self.conv, self.bn, self.relu = conv, bn, relu
-        self.cout, self.cin_g, self.k = conv.out_channels, conv.in_channels // conv.groups, conv.kernel_size[0]
-        self.stride = conv.stride[0]
-        self.kind = 2 if stem else (1 if conv.groups > 1 else 0)
-        self.cpad = round_up(self.cout, 16)
-        if self.kind == 1:
-            self.kpad = 0
-            self.pack = torch.zeros(self.k * self.k * self.cpad, dtype=torch.float32, device=dev)
-        else:
-            self.kpad = 64 if stem else round_up(self.cin_g, 32)
-            self.pack = torch.zeros((self.cpad // 16) * (self.kpad // 32) * 64 * 8, dtype=torch.int16, device=dev)
+        super().__init__(conv, dev, stem, 32, torch.int16)
+        self.bn, self.relu = bn, relu
         self.biasf = torch.zeros(self.cpad, dtype=torch.float32, device=dev)
 
     def desc(self):
@@ -107,29 +93,17 @@ class Bf16Inference:
         # act='hswish' networks (frostnet.py ConvBNHswish): the layer kernels take the activation as a code (0 none, 1 ReLU, 2 hard-swish); the fused
         # bottleneck kernels (frost_infer_block / _block_w) are written for ReLU, so such a network runs layer by layer
         self.hswish = getattr(model, "act", "relu") == "hswish"
-        A = 2 if self.hswish else 1
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError("Bf16Inference needs the model on the GPU (no CPU fallback on the product path)")
         self.model, self.device = model, p.device
         self.layers = []
-        self.stem = self._add(model.conv1.conv, A, stem=True)
-        self.blocks, self.stage_ends = [], []
-        for stage in (model.layer1, model.layer2, model.layer3, model.layer4, model.layer5):
-            for blk in stage:
-                ent = dict(blk=blk, squeeze=None, conv1=None)
-                if blk.expand_ratio != 1:
-                    if blk.block_type == "CAS":
-                        ent["squeeze"] = self._add(blk.squeeze_conv.conv, A)
-                    ent["conv1"] = self._add(blk.conv1.conv, A)
-                ent["conv2"] = self._add(blk.conv2.conv, A)
-                ent["reduce"] = self._add(blk.reduce_conv.conv, 0)
-                self.blocks.append(ent)
-            self.stage_ends.append(len(self.blocks) - 1)
-        # the classifier's tail; the feature backbone and the detector (Bf16SSDInference) have none and bind their own layers behind the trunk
-        self.last = self._add(model.last_layer.conv, A) if hasattr(model, "last_layer") else None
-        self.fc = model.classifier[2] if hasattr(model, "classifier") else None
-        self._bind_extra()
+        # the classifier's tail where the tree has one (the feature backbone and the detector have none); a detector's extras and heads behind the trunk in the
+        # same descriptor table (one prep launch for all of them)
+        plan = plan_tree(model)
+        self.stem, self.blocks, self.last = bind_trunk(plan, self._add)
+        self.stage_ends, self.fc = plan.stage_ends, plan.classifier
+        self.extras, self.heads = bind_detector(plan, self._add)
         self._table, self._ptrs, self._versions = None, None, None
 
     def _prepare_weights(self):
@@ -154,11 +128,8 @@ class Bf16Inference:
     def refresh(self):
         self._versions = None
 
-    def _bind_extra(self):
-        """Layers behind the trunk that a subclass adds to the same descriptor table (one prep launch for all of them)."""
-
-    def _add(self, seq, relu, stem=False):
-        l = _ILayer(seq, relu, self.device, stem)
+    def _add(self, name, wrapper, kind):
+        l = _ILayer(wrapper.conv, act_code(wrapper), self.device, kind == "stem")
         self.layers.append(l)
         return l
 
@@ -169,8 +140,7 @@ class Bf16Inference:
         return y
 
     def _dw(self, l, x, n, h, w):
-        pad = (l.k - 1) // 2
-        ho, wo = (h + 2 * pad - l.k) // l.stride + 1, (w + 2 * pad - l.k) // l.stride + 1
+        ho, wo = conv_out_hw(h, w, l.k, l.stride)
         y = torch.empty(n * ho * wo * l.cout + 64, dtype=torch.int16, device=self.device)
         call("frost_infer_dw", ptr(x), ptr(l.pack), ptr(l.biasf), n, h, w, l.cout, l.k, l.stride, int(l.relu), ptr(y), stream())
         return y, ho, wo
@@ -199,8 +169,7 @@ class Bf16Inference:
         """The same bottleneck as ONE launch of frost_infer_block with the spatial output tile `tile`."""
         l2, l3, sq, l1 = ent["conv2"], ent["reduce"], ent["squeeze"], ent["conv1"]
         r = sq.cout if sq is not None else 0
-        pad = (l2.k - 1) // 2
-        h2, w2 = (h + 2 * pad - l2.k) // l2.stride + 1, (w + 2 * pad - l2.k) // l2.stride + 1
+        h2, w2 = conv_out_hw(h, w, l2.k, l2.stride)
         out = torch.empty(n * h2 * w2 * l3.cout + 64, dtype=torch.int16, device=self.device)
         call("frost_infer_block", ptr(a), ptr(sq.pack) if sq is not None else None, ptr(sq.biasf) if sq is not None else None,
              ptr(l1.pack) if l1 is not None else None, ptr(l1.biasf) if l1 is not None else None, ptr(l2.pack), ptr(l2.biasf),
@@ -211,8 +180,7 @@ class Bf16Inference:
     def _block_wave(self, ent, a, c, n, h, w, tile):
         """A bottleneck without a squeeze conv as ONE launch of frost_infer_block_w: one wave per (th, tw) output tile, no workgroup barriers."""
         l2, l3, l1 = ent["conv2"], ent["reduce"], ent["conv1"]
-        pad = (l2.k - 1) // 2
-        h2, w2 = (h + 2 * pad - l2.k) // l2.stride + 1, (w + 2 * pad - l2.k) // l2.stride + 1
+        h2, w2 = conv_out_hw(h, w, l2.k, l2.stride)
         out = torch.empty(n * h2 * w2 * l3.cout + 64, dtype=torch.int16, device=self.device)
         call("frost_infer_block_w", ptr(a), ptr(l1.pack) if l1 is not None else None, ptr(l1.biasf) if l1 is not None else None, ptr(l2.pack), ptr(l2.biasf),
              ptr(l3.pack), ptr(l3.biasf), n, h, w, c, l2.cout, l3.cout, l2.k, l2.stride, 0 if ent["blk"].reduction else 1, tile[1], tile[2], ptr(out), stream())
@@ -286,7 +254,7 @@ class Bf16Inference:
         """Stem + the five stages -> [(activation NHWC bf16, channels, h, w)] at the end of every stage (the last entry is the trunk's output)."""
         n, _, h, w = x.shape
         self._prepare_weights()
-        ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+        ho, wo = conv_out_hw(h, w, 3, 2)
         npix = n * ho * wo
         if _STEM_DIRECT and L.load_library().frost_infer_stem_ok(self.stem.cout):
             a = torch.empty(npix * self.stem.cout, dtype=torch.int16, device=self.device)
@@ -314,7 +282,7 @@ class Bf16Inference:
         """[x1, x2, x3, x5] of the feature backbone (frostnet_features.py:342-352: strides 4 / 8 / 16 / 32, x4 skipped) as fp32 NCHW."""
         self._check_input(x)
         outs = self._trunk(x)
-        return [self._nchw_f32(outs[i][0], x.shape[0], *outs[i][1:]) for i in (0, 1, 2, 4)]
+        return [self._nchw_f32(outs[i][0], x.shape[0], *outs[i][1:]) for i in FEATURE_TAPS]
 
     @torch.no_grad()
     def __call__(self, x):
@@ -368,13 +336,7 @@ class Bf16SSDInference(Bf16Inference):
         if getattr(model, "act", "relu") == "hswish":
             raise RuntimeError("the detector's bf16 inference path is written for ReLU networks")
         super().__init__(model)
-
-    def _bind_extra(self):
-        m = self.model
-        self.anchors, self.num_classes = list(m.ANCHORS), int(m.num_classes)
-        self.extras = [(self._add(e.pw1.conv, 1), self._add(e.dw.conv, 1), self._add(e.pw2.conv, 1)) for e in m.extras]
-        self.heads = [(self._add(l.dw.conv, 1), self._add(l.pw.conv, 0), self._add(c.dw.conv, 1), self._add(c.pw.conv, 0)) for l, c in zip(m.loc, m.conf)]
-        self._offsets = {}
+        self.anchors, self.num_classes, self._offsets = list(model.ANCHORS), int(model.num_classes), {}
 
     def head_offsets(self, sizes):
         """(prior offsets, P) of the source maps `sizes`, built once per input size (host integers: the launches take them as arguments)."""
@@ -407,7 +369,7 @@ class Bf16SSDInference(Bf16Inference):
         """The six source maps [(activation, channels, h, w)]: stage ends 1, 2 and 4 (0-based) of the trunk, then the output of every extra stage."""
         n = x.shape[0]
         outs = self._trunk(x)
-        sources = [outs[1], outs[2], outs[4]]
+        sources = [outs[i] for i in SSD_TAPS]
         a, c, h, w = outs[4]
         for pw1, dw, pw2 in self.extras:
             t = self._pw(pw1, a, n * h * w, c)

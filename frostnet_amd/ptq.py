@@ -138,28 +138,19 @@ def _observer_ok(obs):
     return type(obs).__name__ == "HistogramObserver" and obs.bins == BINS and obs.upsample_rate == UPSAMPLE and obs.dtype == torch.quint8
 
 
-from .float_train import FAct, round_up, EMIT, DESC_BYTES      # noqa: E402  (after the CPU definition: importing it needs no device)
+from .float_train import FAct, EMIT, DESC_BYTES      # noqa: E402  (after the CPU definition: importing it needs no device)
+from .topology import FloatLayer, bind_trunk, conv_out_hw, model_signature, plan_tree      # noqa: E402
 
 
-class _PLayer:
+class _PLayer(FloatLayer):
     """One fused layer (Conv2d with the BatchNorm folded into weight and bias, ReLU or not) on the fp32 float kernels."""
-
     def __init__(self, name, mod, dev, stem=False):
         relu = type(mod).__name__ == "ConvReLU2d"
         conv = mod[0] if relu else mod
         if not isinstance(conv, torch.nn.Conv2d) or conv.bias is None:
             raise RuntimeError(f"{name}: the calibration path expects the fused model (Conv2d with the BatchNorm folded in); call ptq_prepare")
-        self.name, self.mod, self.conv, self.relu = name, mod, conv, 1 if relu else 0
-        self.cout, self.cin_g, self.k = conv.out_channels, conv.in_channels // conv.groups, conv.kernel_size[0]
-        self.stride = conv.stride[0]
-        self.kind = 2 if stem else (1 if conv.groups > 1 else 0)
-        self.cpad = round_up(self.cout, 16)
-        if self.kind == 1:
-            self.kpad = 0
-            self.pack = torch.zeros(self.k * self.k * self.cpad, dtype=torch.float32, device=dev)
-        else:
-            self.kpad = 64 if stem else round_up(self.cin_g, 16)
-            self.pack = torch.zeros((self.cpad // 16) * (self.kpad // 16) * 1024, dtype=torch.uint8, device=dev)
+        super().__init__(conv, dev, stem, 16)
+        self.name, self.mod, self.relu = name, mod, 1 if relu else 0
         self.stat = torch.zeros(8 * 4 * self.cpad, dtype=torch.float64, device=dev)
         self.coef = torch.zeros(8 * self.cpad, dtype=torch.float32, device=dev)
         self.site = None
@@ -187,25 +178,10 @@ class PtqRunner:
         self.layers, self._obs = [], []
         nsites = sum(1 for m in model.modules() if type(m).__name__ == "HistogramObserver")
         self.qa = PtqArena(nsites, dev)
-        self.q_in = self._site("quant", model.quant)
-        self.stem = self._add("conv1", model.conv1.conv[0], stem=True)
-        self.blocks = []
-        for lname in ("layer1", "layer2", "layer3", "layer4", "layer5"):
-            for bi, blk in enumerate(getattr(model, lname)):
-                pre = f"{lname}.{bi}"
-                ent = dict(blk=blk, squeeze=None, conv1=None, q_cat=None, q_add=None)
-                if blk.expand_ratio != 1:
-                    if blk.block_type == "CAS":
-                        ent["squeeze"] = self._add(pre + ".squeeze_conv", blk.squeeze_conv.conv[0])
-                        ent["q_cat"] = self._site(pre + ".quant_cat", blk.quant_cat)
-                    ent["conv1"] = self._add(pre + ".conv1", blk.conv1.conv[0])
-                ent["conv2"] = self._add(pre + ".conv2", blk.conv2.conv[0])
-                ent["reduce"] = self._add(pre + ".reduce_conv", blk.reduce_conv.conv[0])
-                if not blk.reduction:
-                    ent["q_add"] = self._site(pre + ".skip_add", blk.skip_add)
-                self.blocks.append(ent)
-        self.last = self._add("last_layer", model.last_layer.conv[0])
-        self.fc = model.classifier[2]
+        plan = plan_tree(model)
+        self.q_in = self._site("quant", plan.quant)
+        self.stem, self.blocks, self.last = bind_trunk(plan, self._add, self._site)
+        self.fc = plan.classifier
         self.q_fc = self._site("classifier.2", self.fc)
         # a block that does not cat / add still owns the FloatFunctional: its observer never sees data on either side (stock convert gives it scale 1, zero-point 0)
         idle = sum((e["q_cat"] is None) + (e["q_add"] is None) for e in self.blocks)
@@ -218,7 +194,7 @@ class PtqRunner:
         for i, l in enumerate(self.layers):
             l.desc_ptr = C.c_void_p(self._table.data_ptr() + i * DESC_BYTES)
         self._err = self.qa.t[:1]
-        self._sig = tuple(p.data_ptr() for p in model.parameters()) + tuple(b.data_ptr() for b in model.buffers())
+        self._sig = model_signature(model)
 
     # ------------------------------------------------------------------------------------------ binding
     def _site(self, name, mod):
@@ -238,15 +214,15 @@ class PtqRunner:
         self._obs.append((name, obs, site))
         return site
 
-    def _add(self, name, mod, stem=False):
-        l = _PLayer(name, mod, self.device, stem)
+    def _add(self, name, wrapper, kind):
+        mod = wrapper.conv[0]
+        l = _PLayer(name, mod, self.device, kind == "stem")
         l.site = self._site(name, mod)
         self.layers.append(l)
         return l
 
     def still_valid(self):
-        m = self.model
-        return self._sig == tuple(p.data_ptr() for p in m.parameters()) + tuple(b.data_ptr() for b in m.buffers())
+        return self._sig == model_signature(self.model)
 
     # ------------------------------------------------------------------------------------------ forward
     def _new(self, n, h, w, c):
@@ -257,9 +233,7 @@ class PtqRunner:
 
     def _conv(self, l, a):
         if l.kind == 1:
-            pad = (l.k - 1) // 2
-            ho, wo = (a.h + 2 * pad - l.k) // l.stride + 1, (a.w + 2 * pad - l.k) // l.stride + 1
-            y = self._new(a.n, ho, wo, l.cout)
+            y = self._new(a.n, *conv_out_hw(a.h, a.w, l.k, l.stride), l.cout)
             call("frost_float_dw_f32", l.desc_ptr, ptr(a.buf), a.n, a.h, a.w, a.c, l.k, l.stride, l.relu, EMIT, None, ptr(y.buf), stream())
         else:
             y = self._new(a.n, a.h, a.w, l.cout)
@@ -285,8 +259,7 @@ class PtqRunner:
         call("frost_float_weight_prep", ptr(self._table), nl, stream())
         call("frost_ptq_coef", ptr(self._table), nl, stream())
         call("frost_ptq_observe_strided", ptr(x), n, c, h, w, *x.stride(), ptr(self.q_in), ptr(self._err), stream())          # QuantStub's observer
-        ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-        col = self._new(n, ho, wo, 64)
+        col = self._new(n, *conv_out_hw(h, w, 3, 2), 64)
         call("frost_float_stem_im2col_f32", ptr(x), n, h, w, *x.stride(), ptr(col.buf), stream())
         a = self._conv(self.stem, col)
         for ent in self.blocks:
@@ -366,7 +339,7 @@ class PtqConvertedRunner(FrostRunner):
             self._build()
             self.convert()
 
-    def _rec(self, name, mod):
+    def _site(self, name, mod):
         """Activation record of a site, frozen: scale / zero-point of the calibrated observer, its own observer flag off."""
         scale, zp, qmax = self._qp[name]
         rec = self.qa.alloc()
@@ -379,11 +352,11 @@ class PtqConvertedRunner(FrostRunner):
         return rec
 
     def _conv_layer(self, name, blk, kind):
-        m = blk.conv[0] if hasattr(blk, "conv") else blk
+        m = blk if kind == "cls" else blk.conv[0]
         relu = type(m).__name__ == "ConvReLU2d"
         conv = m[0] if relu else m
         l = ConvLayer(name, kind, conv.weight, None, None, None, None, None, conv.bias, conv.kernel_size[0], conv.stride[0], relu, self.qa.alloc(),
-                      self._rec(name, m))
+                      self._site(name, m))
         if self._pc:
             l.per_channel = True
             l.wmin = torch.full((l.cout,), float("inf"), dtype=torch.float32, device=self.device)
@@ -391,33 +364,11 @@ class PtqConvertedRunner(FrostRunner):
         l.qmod = m
         return self.E.add_layer(l)
 
-    def _build(self):
-        m = self.model
-        self.qa = QArena(2 * len(self._qp) + 16, self.device)
-        self.rule127 = False
-        self.q_in = self._rec("quant", m.quant)
-        self.stem = self._conv_layer("conv1", m.conv1, "stem")
-        self.blocks = []
-        for lname in ("layer1", "layer2", "layer3", "layer4", "layer5"):
-            for bi, b in enumerate(getattr(m, lname)):
-                pre = f"{lname}.{bi}"
-                d = dict(mod=b, squeeze=None, conv1=None, q_cat=None, q_add=None)
-                if b.expand_ratio != 1:
-                    if b.block_type == "CAS":
-                        d["squeeze"] = self._conv_layer(pre + ".squeeze_conv", b.squeeze_conv, "pw")
-                        d["q_cat"] = self._rec(pre + ".quant_cat", b.quant_cat)
-                    d["conv1"] = self._conv_layer(pre + ".conv1", b.conv1, "pw")
-                d["conv2"] = self._conv_layer(pre + ".conv2", b.conv2, "dw")
-                d["reduce"] = self._conv_layer(pre + ".reduce_conv", b.reduce_conv, "pw")
-                if not b.reduction:
-                    d["q_add"] = self._rec(pre + ".skip_add", b.skip_add)
-                self.blocks.append(d)
-        self.last = self._conv_layer("last_layer", m.last_layer, "pw")
-        self.cls = self._conv_layer("classifier.2", m.classifier[2], "cls")
-        self.drop_rate = float(m.classifier[1].p)
-        self.E.rule127 = 0
-        self._sig = tuple(p.data_ptr() for p in m.parameters()) + tuple(b.data_ptr() for b in m.buffers())
-        self._params = list(m.parameters())
+    def _new_arena(self):
+        return QArena(2 * len(self._qp) + 16, self.device)
+
+    def _bind_params(self, params):
+        self._params = params          # a converted model has no gradients: no arena
 
     def _site_qparams(self, obs):
         rec = self._recs.get(id(obs))

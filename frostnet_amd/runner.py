@@ -13,6 +13,7 @@ import torch
 
 from . import _lib as L
 from .engine import ConvLayer, Engine, QArena
+from .topology import FEATURE_TAPS, SSD_TAPS, GradArena, bind_block, bind_detector, bind_trunk, model_signature, plan_block, plan_tree
 
 
 _STEM_COL_EARLY = os.environ.get("FROST_STEM_COL_EARLY", "1") != "0"      # the stem's im2col in front of the join with the weight-preparation stream (A/B)
@@ -116,7 +117,7 @@ def _is_fused_fq(fq):
     return type(fq).__name__ == "FusedMovingAvgObsFakeQuantize"
 
 
-class FrostRunner:
+class FrostRunner(GradArena):
     converted = False        # hip_convert() ran: forward() computes the converted int8 model (class-level defaults: for_block builds a runner without __init__)
     converted_fb = False     # ... in the FBGEMM engine's form (a per-channel model)
 
@@ -136,7 +137,6 @@ class FrostRunner:
         if self.device.type != "cuda":
             raise RuntimeError(f"FrostRunner needs the model on the HIP device (parameters are on {self.device})")
         self.E = Engine(self.device)
-        self._sig = tuple(p.data_ptr() for p in params) + tuple(b.data_ptr() for b in model.buffers())
         self._build()
 
     @classmethod
@@ -146,19 +146,10 @@ class FrostRunner:
         r = cls.__new__(cls)
         r.model, r.device = block, next(block.parameters()).device
         r.E, r.qa, r.rule127 = Engine(r.device), QArena(32, r.device), False
-        r.block = r._bind_block("B", block)
+        r.block = bind_block(plan_block("B", block), r._conv_layer, r._site, key="mod")
         r.E.rule127 = 1 if r.rule127 else 0
-        r._make_grad_arena(list(block.parameters()))
+        r._bind_params(list(block.parameters()))
         return r
-
-    def _make_grad_arena(self, params):
-        """Flat gradient arena, parameter order = model.parameters() (the reference's registration order)."""
-        self.grad_arena = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=self.device)
-        self._grad_views, off = [], 0
-        for p in params:
-            self._grad_views.append(self.grad_arena[off: off + p.numel()].view_as(p))
-            off += p.numel()
-        self._params = params
 
     def read_flags(self):
         """ONE device -> host read of the enable-flag columns of the qrecord arena (the torch `observer_enabled` / `fake_quant_enabled` buffers are
@@ -201,9 +192,7 @@ class FrostRunner:
         set_rng_state(self, state)
 
     def still_valid(self):
-        m = self.model
-        sig = tuple(p.data_ptr() for p in m.parameters()) + tuple(b.data_ptr() for b in m.buffers())
-        return sig == self._sig
+        return model_signature(self.model) == self._sig
 
     # ------------------------------------------------------------------------------------------ binding
     @staticmethod
@@ -272,18 +261,24 @@ class FrostRunner:
         obs._buffers["max_val"] = rec[L.Q_MAX]
         return rec
 
+    def _site(self, name, mod):
+        """Activation site of a QuantStub / FloatFunctional: the next record of the arena, bound to the module's FakeQuantize."""
+        return self._bind_fq(mod.activation_post_process, self.qa.alloc())
+
     def _conv_layer(self, name, blk, kind):
-        m = blk.conv[0]   # nniqat.ConvBnReLU2d / ConvBn2d
+        m = blk if kind == "cls" else blk.conv[0]   # nniqat.ConvBnReLU2d / ConvBn2d; the classifier: nnqat.Conv2d with a bias, no BatchNorm
+        bn = getattr(m, "bn", None)
         relu = type(m).__name__ == "ConvBnReLU2d"
         pc = self._is_per_channel(m.weight_fake_quant)
         qw = self.qa.alloc() if pc else self._bind_fq(m.weight_fake_quant, self.qa.alloc())
         qy = self._bind_fq(m.activation_post_process, self.qa.alloc())
-        self.rule127 = self.rule127 or _is_fused_fq(m.weight_fake_quant)
-        l = ConvLayer(name, kind, m.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var,
-                      m.bn.num_batches_tracked, None, m.kernel_size[0], m.stride[0], relu, qw, qy)
+        if bn is not None:
+            self.rule127 = self.rule127 or _is_fused_fq(m.weight_fake_quant)
+        norm = (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, None) if bn is not None else (None,) * 5 + (m.bias,)
+        l = ConvLayer(name, kind, m.weight, *norm, m.kernel_size[0], m.stride[0], relu, qw, qy)
         if pc:
             self._bind_weight_per_channel(m.weight_fake_quant, qw, l)
-        l.bn_mod = m.bn
+        l.bn_mod = bn
         l.qmod = m
         act = getattr(blk, "act", None)
         if act is not None and type(act).__name__ == "Hswish":
@@ -300,19 +295,6 @@ class FrostRunner:
         if l.hswish is not None:
             y = self.E.hswish(y, l.hswish[0], l.hswish[1], l.hswish[2], obs)
         return y
-
-    def _bind_block(self, pre, b):
-        d = dict(mod=b, squeeze=None, conv1=None, q_cat=None, q_add=None)
-        if b.expand_ratio != 1:
-            if b.block_type == "CAS":
-                d["squeeze"] = self._conv_layer(pre + ".squeeze_conv", b.squeeze_conv, "pw")
-                d["q_cat"] = self._bind_fq(b.quant_cat.activation_post_process, self.qa.alloc())
-            d["conv1"] = self._conv_layer(pre + ".conv1", b.conv1, "pw")
-        d["conv2"] = self._conv_layer(pre + ".conv2", b.conv2, "dw")
-        d["reduce"] = self._conv_layer(pre + ".reduce_conv", b.reduce_conv, "pw")
-        if not b.reduction:
-            d["q_add"] = self._bind_fq(b.skip_add.activation_post_process, self.qa.alloc())
-        return d
 
     def block_forward(self, d, inp, training, obs):
         """CascadePreExBottleneck.forward (frostnet.py:124-145) on the engine."""
@@ -338,56 +320,34 @@ class FrostRunner:
             out = self._conv(d["reduce"], out, training, obs)
         return out
 
-    def _build(self):
+    def _new_arena(self):
         m = self.model
-        blocks = [b for layer in (m.layer1, m.layer2, m.layer3, m.layer4, m.layer5) for b in layer]
         nsites = sum(1 for mod in m.modules() if hasattr(mod, "observer_enabled")) + 16     # every FakeQuantize of the tree + slack
         nsites += sum(1 for mod in m.modules() if type(mod).__name__ == "Hswish")              # + the derived output record of every hard-swish
-        self.qa = QArena(nsites, self.device)
-        self.rule127 = False
-        self.q_in = self._bind_fq(m.quant.activation_post_process, self.qa.alloc())
-        self.stem = self._conv_layer("conv1", m.conv1, "stem")
-        self.blocks = []
-        for lname in ("layer1", "layer2", "layer3", "layer4", "layer5"):
-            for bi, b in enumerate(getattr(m, lname)):
-                self.blocks.append(self._bind_block(f"{lname}.{bi}", b))
-        self.last = self._conv_layer("last_layer", m.last_layer, "pw") if hasattr(m, "last_layer") else None
-        self.cls = None
-        if hasattr(m, "classifier"):
-            c = m.classifier[2]
-            pc = self._is_per_channel(c.weight_fake_quant)
-            qw = self.qa.alloc() if pc else self._bind_fq(c.weight_fake_quant, self.qa.alloc())
-            qy = self._bind_fq(c.activation_post_process, self.qa.alloc())
-            self.cls = self.E.add_layer(ConvLayer("classifier.2", "cls", c.weight, None, None, None, None, None, c.bias,
-                                                  1, 1, False, qw, qy))
-            if pc:
-                self._bind_weight_per_channel(c.weight_fake_quant, qw, self.cls)
-            self.cls.qmod = c
-            self.drop_rate = float(m.classifier[1].p)
-        self._bind_extra()
-        self.E.rule127 = 1 if self.rule127 else 0
-        # buffers were re-pointed: refresh the validity signature
-        self._sig = tuple(p.data_ptr() for p in m.parameters()) + tuple(b.data_ptr() for b in m.buffers())
-        self._make_grad_arena(list(m.parameters()))
+        return QArena(nsites, self.device)
 
-    def _bind_extra(self):
-        """Subclasses bind further layers here (SSDRunner: extras + prediction heads)."""
+    def _build(self):
+        """Binds the tree in topology's order: QuantStub, stem, bottlenecks, last_layer, classifier (a classification model), extras and heads (a detector)."""
+        plan = plan_tree(self.model)
+        self.qa = self._new_arena()
+        self.rule127 = False
+        self.q_in = self._site("quant", plan.quant)
+        self.stem, self.blocks, self.last = bind_trunk(plan, self._conv_layer, self._site, key="mod")
+        self.stage_ends = plan.stage_ends
+        self.cls = None
+        if plan.classifier is not None:
+            self.cls = self._conv_layer("classifier.2", plan.classifier, "cls")
+            self.drop_rate = plan.drop_rate
+        self.extras, self.heads = bind_detector(plan, self._conv_layer)
+        self.E.rule127 = 1 if self.rule127 else 0
+        self._sig = model_signature(self.model)          # (after the buffers were re-pointed)
+        self._bind_params(list(self.model.parameters()))
 
     def enable_data_parallel(self, nbuckets=4, group=None):
         """Attach the bucketed, backward-overlapped gradient all-reduce (frostnet_amd.parallel.GradSync)."""
-        from .parallel import GradSync
-        offs, off = {}, 0
-        for p in self._params:
-            offs[p.data_ptr()] = off
-            off += p.numel()
-        self.grad_sync = GradSync(self.grad_arena, list(offs.values()), nbuckets, group)
+        offs = {p.data_ptr(): off for p, off in zip(self._params, self._grad_offsets)}
         self.E.on_layer_grads = lambda l: self.grad_sync.ready(offs[l.w.data_ptr()])
-        return self.grad_sync
-
-    def bind_grads(self):
-        for p, v in zip(self._params, self._grad_views):
-            if p.grad is None or p.grad.data_ptr() != v.data_ptr():
-                p.grad = v
+        return self._attach_grad_sync(nbuckets, group)
 
     def _carry_over(self):
         """torch semantics: `backward()` ACCUMULATES into p.grad until `zero_grad()`.  The kernels write (=) into the flat arena, so the
@@ -469,13 +429,6 @@ class FrostRunner:
                 taps.append(a)
         return a, feats
 
-    def _stage_ends(self, feats):
-        ends, i = [], 0
-        for lname in ("layer1", "layer2", "layer3", "layer4", "layer5"):
-            i += len(getattr(self.model, lname))
-            ends.append(feats[i - 1])
-        return ends
-
     def _forward_converted(self, x, taps=None):
         a, _ = self._trunk_converted(x, taps)
         fb = self.converted_fb
@@ -487,9 +440,8 @@ class FrostRunner:
     def _features_converted(self, x):
         """The converted features backbone (frostnet_features.py:350: [x1, x2, x3, x5], DeQuantStub on each)."""
         _, feats = self._trunk_converted(x)
-        ends = self._stage_ends(feats)
         self.E.tape = []
-        return [ends[0], ends[1], ends[2], ends[4]]
+        return [feats[self.stage_ends[i]] for i in FEATURE_TAPS]
 
     def export_converted(self):
         """The state_dict of `torch.quantization.convert(model.eval())` (what Classification/evaluate.py:140-143 and Object_Detection/qeval_convert.py save as the
@@ -619,10 +571,9 @@ class FrostRunner:
         if x.dtype != torch.float32:
             x = x.float()
         _, feats = self._trunk(x, self.model.training)
-        ends = self._stage_ends(feats)
         if not record:
             self.E.tape = []
-        return [ends[0], ends[1], ends[2], ends[4]]          # x4 is skipped (frostnet_features.py:350)
+        return [feats[self.stage_ends[i]] for i in FEATURE_TAPS]
 
     def _forward_impl(self, x, record):
         training = self.model.training
@@ -679,21 +630,11 @@ class SSDRunner(FrostRunner):
     """frostnet_amd.ssdlite.SSDLiteFrostNet on the engine: backbone (sources at strides 8/16/32) + SSDLite extras + separable prediction heads,
     every layer a fake-quantised ConvBN(ReLU) on the int8-MFMA / LDS depthwise kernels; twelve dequantised maps come back."""
 
-    def _bind_extra(self):
-        m = self.model
-        self.extras = [[self._conv_layer(f"extras.{i}.pw1", e.pw1, "pw"), self._conv_layer(f"extras.{i}.dw", e.dw, "dw"),
-                        self._conv_layer(f"extras.{i}.pw2", e.pw2, "pw")] for i, e in enumerate(m.extras)]
-        self.heads = []
-        for i, (l, c) in enumerate(zip(m.loc, m.conf)):
-            self.heads.append((self._conv_layer(f"loc.{i}.dw", l.dw, "dw"), self._conv_layer(f"loc.{i}.pw", l.pw, "pw"),
-                               self._conv_layer(f"conf.{i}.dw", c.dw, "dw"), self._conv_layer(f"conf.{i}.pw", c.pw, "pw")))
-
     def _sources_converted(self, x):
         """The six source activations of the converted detector: stage ends 1, 2 and 4 (0-based) of the trunk, then the output of every extra stage."""
         E, fb = self.E, self.converted_fb
         a, feats = self._trunk_converted(x)
-        ends = self._stage_ends(feats)
-        sources = [ends[1], ends[2], ends[4]]
+        sources = [feats[self.stage_ends[i]] for i in SSD_TAPS]
         for pw1, dw, pw2 in self.extras:
             a = E.conv_converted(pw2, E.conv_converted(dw, E.conv_converted(pw1, a, fb), fb), fb)
             sources.append(a)
@@ -781,8 +722,7 @@ class SSDRunner(FrostRunner):
             x = x.float()
         a, feats = self._trunk(x, training)
         obs, E = self._obs, self.E
-        ends = self._stage_ends(feats)
-        sources = [ends[1], ends[2], ends[4]]
+        sources = [feats[self.stage_ends[i]] for i in SSD_TAPS]
         for pw1, dw, pw2 in self.extras:
             a = E.conv(pw2, E.conv(dw, E.conv(pw1, a, training, obs), training, obs), training, obs)
             sources.append(a)
