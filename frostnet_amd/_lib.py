@@ -124,6 +124,9 @@ _PROTOS = {
     "frost_voc_update": [P, P, P, P, P, I, I, I, I, I, F, F, I, I, L, P, P, P],
     "frost_voc_ap": [P, P, I, L, I, I, P, P, P],
     "frost_voc_reset": [P, P, I, L, P],
+    "frost_seg_workspace_bytes": [],
+    "frost_seg_state_words": [I],
+    "frost_seg_forward": [P, I, I, I, I, L, L, L, L, P, I, I, I, P, P, P, P, P, P],
     "frost_aug_plan_words": [],
     "frost_aug_plan": [P, P, P, I, I, P, P, P, P, P],
     "frost_aug_apply": [P, P, P, I, I, I, I, F, F, F, I, P, P],

@@ -11,6 +11,8 @@
     The running sums stay on the device: ONE host read per epoch instead of the reference's three `.item()` per iteration.
   * `val_detector` -- the detector's validation pass, Object_Detection/qeval_convert.py:348-396 (`test_net`) as qtrainval.py:314 calls it: detections on the
     device, scored by a `VOCEvaluator` whose state stays on the device; ONE host read per evaluation instead of one per image and class.
+  * `train_seg` / `val_seg` -- the segmentation epoch loops, Semantic_Segmentation/utilities/train_eval_seg.py: mean IoU from a `seg.SegMeter` on the device, the
+    sample-weighted loss sum on the device; ONE host read per epoch instead of one `.item()` and three host histograms per iteration.
   * `checkpoint_state` / `save_checkpoint` / `load_checkpoint` -- Classification/train.py:193-223, helper_functions.py:400-407: the reference's
     dictionary keys, plus `hip_rng` (dropout Philox seed + draw count; the GradBoost stream resumes from the optimizer's step count).
 """
@@ -326,6 +328,63 @@ def val_detector(loader, model, evaluator, top_k=200, conf_thresh=0.01, nms_thre
     if vals[0] != 0:
         raise RuntimeError(evaluator.OVERFLOW_MSG)
     return vals[1], vals[2:]
+
+
+def _seg_epoch(model, loader, optimizer, criterion, num_classes, device):
+    """The body of train_seg (optimizer given) and val_seg: the counts in a `SegMeter`, the sample-weighted loss sum on the device, ONE host read at the end."""
+    from .seg import SegMeter, SegmentationLoss
+    dev = device
+    if dev is None:
+        p = next(model.parameters(), None)
+        dev = p.device if p is not None else None
+    meter, loss_sum, samples = None, None, 0
+    fused = isinstance(criterion, SegmentationLoss)          # the criterion's own launch counts the batch
+    saved = criterion.meter if fused else None
+    try:
+        for inputs, target in loader:
+            if dev is not None:
+                inputs, target = inputs.to(dev, non_blocking=True), target.to(dev, non_blocking=True)
+            if meter is None:
+                meter = SegMeter(num_classes, target.device)
+                if fused:
+                    criterion.meter = meter
+            outputs = model(inputs)
+            if isinstance(outputs, list):
+                outputs = tuple(outputs)
+            if criterion is not None:
+                loss = criterion(outputs, target)
+                loss = loss.mean() if loss.dim() else loss
+                w = loss.detach().double() * inputs.size(0)
+                loss_sum = w if loss_sum is None else loss_sum + w
+            if not fused:
+                meter.update(outputs, target)
+            samples += inputs.size(0)
+            if optimizer is not None:
+                optimizer.zero_grad()
+                loss.backward()
+                optimizer.step()
+    finally:
+        if fused:
+            criterion.meter = saved
+    if meter is None:
+        raise ValueError("empty loader")
+    miou = meter.compute()
+    return miou, (float(loss_sum) / samples if loss_sum is not None else 0)
+
+
+def train_seg(model, dataset_loader, optimizer, criterion, num_classes, epoch=0, device=None):
+    """One training epoch of Semantic_Segmentation/utilities/train_eval_seg.py:train_seg for any module that returns logits (or a tuple of them) -> (mean IoU in
+    percent over the epoch, sample-weighted mean loss).  With a `seg.SegmentationLoss` criterion the loss launch also counts the batch; any other criterion is
+    followed by `SegMeter.update`.  `device` defaults to the model's."""
+    model.train()
+    return _seg_epoch(model, dataset_loader, optimizer, criterion, num_classes, device)
+
+
+def val_seg(model, dataset_loader, criterion=None, num_classes=21, device=None):
+    """train_eval_seg.py:val_seg -> (mean IoU in percent, sample-weighted mean loss, or 0 without a criterion), under `torch.no_grad()`."""
+    model.eval()
+    with torch.no_grad():
+        return _seg_epoch(model, dataset_loader, None, criterion, num_classes, device)
 
 
 def _is_plain_ce(criterion):

@@ -44,7 +44,8 @@ extern "C" {
  *          New entries (additive): frost_float_ssd_gather[_f32] / frost_float_ssd_scatter[_f32] with the FrostSSDMap table (the float SSDLite detector).
  *          New entries (additive): frost_voc_update / frost_voc_ap / frost_voc_reset (the PASCAL VOC mean-AP evaluator).
  *          New entries (additive): frost_aug_plan / frost_aug_apply / frost_aug_plan_words (SSD training-time augmentation, the FROST_AUG_* plan record).
- *          New entries (additive): frost_caug_plan / frost_caug_eval_plan / frost_caug_apply / frost_caug_plan_words (the classifier's input pipeline, FROST_CAUG_*). */
+ *          New entries (additive): frost_caug_plan / frost_caug_eval_plan / frost_caug_apply / frost_caug_plan_words (the classifier's input pipeline, FROST_CAUG_*).
+ *          New entries (additive): frost_seg_forward / frost_seg_workspace_bytes / frost_seg_state_words (segmentation criterion and mean-IoU counts). */
 #ifndef FROST_DWQ_NC          /* (a -D override is a dev A/B build: the binding must be told the same value, FROST_DWQ_NC / FROST_COEF_ROWS_ALLOC / FROST_STATS_TABLES in the environment) */
 #define FROST_DWQ_NC 4
 #endif
@@ -806,6 +807,25 @@ int frost_voc_update(const float* detections, const float* gt, const uint8_t* di
 int frost_voc_ap(const uint64_t* sorted_records, const int32_t* ctr, int c, int64_t capacity, int bkg_label, int use_07_metric, double* ap, int64_t* counts,
                  void* stream);
 int frost_voc_reset(uint64_t* records, int32_t* ctr, int c, int64_t capacity, void* stream);
+
+/* ---- Segmentation criterion and mean-IoU counts, bilinear upsampling fused in (Semantic_Segmentation/loss_fns/segmentation_loss.py 'ce',
+ * utilities/metrics/segmentation_miou.py; the definition, operation by operation, is frostnet_amd/seg.py: seg_reference) ----------------------------------------
+ * logits fp32 [n][c][h][w] addressed through the element strides sn, sc, sh, sw (contiguous NCHW and channels-last both work), target [n][H][W] contiguous, int64
+ * (target_bytes 8) or uint8 (1), H >= h, W >= w, 2 <= c <= 255, class_wts [c] or NULL for ones.  u = bilinear(logits -> H x W), align_corners = True: source
+ * coordinate dst * (in - 1) / (out - 1), 0 when out == 1; equal sizes are the identity and take a one-read path.  A pixel is valid iff target < c (255 = ignore; any
+ * other value >= c is outside the contract: treated as ignored, counted in the state's bad_targets word, never an index).
+ *   loss [1]  = sum_valid wt[t] (lse(u) - u[t]) / W_sum, W_sum = sum_valid wt[t]; NaN when W_sum == 0
+ *   dx        = bilinear^T(wt[t] (softmax(u) - onehot(t)) / W_sum), the shape and strides of logits, every element written; zeros when W_sum == 0
+ *   state     int64 [3 c + 2] = {area_inter [c], area_pred [c], area_mask [c], batches, bad_targets}, ACCUMULATED: over the valid pixels, with pred = argmax_c u
+ *             (the lowest index among equal values), area_pred[pred]++, area_mask[t]++, area_inter[t]++ if pred == t; batches += 1
+ * Any of loss, dx, state may be NULL.  workspace: the library's workspace byte count, zeroed once by the caller, private to one stream.  Nothing of size n c H W is
+ * read or written; loss, dx and the counts are bit-identical from run to run (no floating-point atomics).  Up to two launches on `stream`, no allocation, nothing
+ * synchronises with the host: legal under stream capture. */
+#define FROST_SEG_MAX_PARTIALS 4096
+int frost_seg_workspace_bytes(void);
+int frost_seg_state_words(int c);
+int frost_seg_forward(const float* logits, int n, int c, int h, int w, int64_t sn, int64_t sc, int64_t sh, int64_t sw, const void* target, int target_bytes,
+                      int H, int W, const float* class_wts, float* loss, float* dx, int64_t* state, void* workspace, void* stream);
 
 /* ---- SSD training-time augmentation (Object_Detection/utils/augmentations.py:400-417 SSDAugmentation, data/__init__.py:30-43 BaseTransform) ------------------------
  * Two halves.  frost_aug_plan takes every random decision of the reference's pipeline, in its order, and writes one record per image plus the transformed targets;

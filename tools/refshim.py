@@ -146,6 +146,17 @@ def load_voc_eval():
     return ns["voc_ap"], ns["voc_eval"]
 
 
+def load_segmentation():
+    """The reference's segmentation criterion, mean-IoU meter and validation loop (Semantic_Segmentation/loss_fns, utilities): (SegmentationLoss, MIOU, val_seg)."""
+    seg = f"{REF}/Semantic_Segmentation"
+    if seg not in sys.path:
+        sys.path.insert(0, seg)
+    from loss_fns.segmentation_loss import SegmentationLoss
+    from utilities.metrics.segmentation_miou import MIOU
+    from utilities.train_eval_seg import val_seg
+    return SegmentationLoss, MIOU, val_seg
+
+
 def load_optimizer():
     if "ref_optimizer" in sys.modules:
         return sys.modules["ref_optimizer"]
