@@ -4,7 +4,8 @@ from ._lib import LIB_PATH, SYMBOLS, load_library  # noqa: F401
 from .augment import BaseTransform, SSDAugmentation, identity_plan, pad_images  # noqa: F401
 from .cls_augment import ClassificationAugmentation, ClassificationEvalTransform  # noqa: F401
 from .seg import SegMeter, SegmentationLoss, seg_reference  # noqa: F401
+from .seg_augment import SegmentationAugmentation, SegmentationEvalTransform, pad_pairs  # noqa: F401
 from .voc_eval import VOCEvaluator  # noqa: F401
 
 __all__ = ["load_library", "LIB_PATH", "SYMBOLS", "VOCEvaluator", "SegmentationLoss", "SegMeter", "seg_reference","SSDAugmentation", "BaseTransform", "identity_plan", "pad_images", "ClassificationAugmentation",
-           "ClassificationEvalTransform"]
+           "ClassificationEvalTransform", "SegmentationAugmentation", "SegmentationEvalTransform", "pad_pairs"]

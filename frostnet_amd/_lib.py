@@ -134,6 +134,10 @@ _PROTOS = {
     "frost_caug_plan": [P, I, I, D, D, D, D, D, D, P, P, P],
     "frost_caug_eval_plan": [P, I, I, I, P, P],
     "frost_caug_apply": [P, P, P, I, I, I, I, F, F, F, F, F, F, I, P, P],
+    "frost_saug_plan_words": [],
+    "frost_saug_plan": [P, I, I, I, D, D, I, P, P, P],
+    "frost_saug_eval_plan": [P, I, I, I, P, P],
+    "frost_saug_apply": [P, P, P, P, I, I, I, I, I, F, F, F, F, F, F, I, I, I, I, P, P, P, P],
     "frost_stats_init_table": [P, P, P, I, P],
     "frost_pw_conv_fwd": [P, P, P, P, L, I, I, I, P, P, P, I, P, P],
     "frost_pw_conv_fwd_fin": [P, P, P, P, L, I, I, P, P, P],

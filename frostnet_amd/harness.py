@@ -330,7 +330,7 @@ def val_detector(loader, model, evaluator, top_k=200, conf_thresh=0.01, nms_thre
     return vals[1], vals[2:]
 
 
-def _seg_epoch(model, loader, optimizer, criterion, num_classes, device):
+def _seg_epoch(model, loader, optimizer, criterion, num_classes, device, transform=None):
     """The body of train_seg (optimizer given) and val_seg: the counts in a `SegMeter`, the sample-weighted loss sum on the device, ONE host read at the end."""
     from .seg import SegMeter, SegmentationLoss
     dev = device
@@ -341,9 +341,16 @@ def _seg_epoch(model, loader, optimizer, criterion, num_classes, device):
     fused = isinstance(criterion, SegmentationLoss)          # the criterion's own launch counts the batch
     saved = criterion.meter if fused else None
     try:
-        for inputs, target in loader:
-            if dev is not None:
-                inputs, target = inputs.to(dev, non_blocking=True), target.to(dev, non_blocking=True)
+        for batch in loader:
+            if transform is None:
+                inputs, target = batch
+                if dev is not None:
+                    inputs, target = inputs.to(dev, non_blocking=True), target.to(dev, non_blocking=True)
+            else:                                # (images uint8 [N, Hmax, Wmax, 3], labels uint8 [N, Hmax, Wmax], sizes int32 [N, 2]): the transform runs on the device, in front of the model
+                images, labels, sizes = batch
+                if dev is not None:
+                    images, labels, sizes = images.to(dev, non_blocking=True), labels.to(dev, non_blocking=True), sizes.to(dev, non_blocking=True)
+                inputs, target = transform(images, labels, sizes)
             if meter is None:
                 meter = SegMeter(num_classes, target.device)
                 if fused:
@@ -372,19 +379,21 @@ def _seg_epoch(model, loader, optimizer, criterion, num_classes, device):
     return miou, (float(loss_sum) / samples if loss_sum is not None else 0)
 
 
-def train_seg(model, dataset_loader, optimizer, criterion, num_classes, epoch=0, device=None):
+def train_seg(model, dataset_loader, optimizer, criterion, num_classes, epoch=0, device=None, transform=None):
     """One training epoch of Semantic_Segmentation/utilities/train_eval_seg.py:train_seg for any module that returns logits (or a tuple of them) -> (mean IoU in
     percent over the epoch, sample-weighted mean loss).  With a `seg.SegmentationLoss` criterion the loss launch also counts the batch; any other criterion is
-    followed by `SegMeter.update`.  `device` defaults to the model's."""
+    followed by `SegMeter.update`.  `device` defaults to the model's.  With a `transform` (a `seg_augment.SegmentationAugmentation`) the loader yields (images uint8,
+    labels uint8, sizes) in `pad_pairs`' format and the transform turns them into the model's input and the target on the device."""
     model.train()
-    return _seg_epoch(model, dataset_loader, optimizer, criterion, num_classes, device)
+    return _seg_epoch(model, dataset_loader, optimizer, criterion, num_classes, device, transform)
 
 
-def val_seg(model, dataset_loader, criterion=None, num_classes=21, device=None):
-    """train_eval_seg.py:val_seg -> (mean IoU in percent, sample-weighted mean loss, or 0 without a criterion), under `torch.no_grad()`."""
+def val_seg(model, dataset_loader, criterion=None, num_classes=21, device=None, transform=None):
+    """train_eval_seg.py:val_seg -> (mean IoU in percent, sample-weighted mean loss, or 0 without a criterion), under `torch.no_grad()`.  `transform` (a
+    `seg_augment.SegmentationEvalTransform`): as in `train_seg`."""
     model.eval()
     with torch.no_grad():
-        return _seg_epoch(model, dataset_loader, None, criterion, num_classes, device)
+        return _seg_epoch(model, dataset_loader, None, criterion, num_classes, device, transform)
 
 
 def _is_plain_ce(criterion):

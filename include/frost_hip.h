@@ -45,7 +45,8 @@ extern "C" {
  *          New entries (additive): frost_voc_update / frost_voc_ap / frost_voc_reset (the PASCAL VOC mean-AP evaluator).
  *          New entries (additive): frost_aug_plan / frost_aug_apply / frost_aug_plan_words (SSD training-time augmentation, the FROST_AUG_* plan record).
  *          New entries (additive): frost_caug_plan / frost_caug_eval_plan / frost_caug_apply / frost_caug_plan_words (the classifier's input pipeline, FROST_CAUG_*).
- *          New entries (additive): frost_seg_forward / frost_seg_workspace_bytes / frost_seg_state_words (segmentation criterion and mean-IoU counts). */
+ *          New entries (additive): frost_seg_forward / frost_seg_workspace_bytes / frost_seg_state_words (segmentation criterion and mean-IoU counts).
+ *          New entries (additive): frost_saug_plan / frost_saug_eval_plan / frost_saug_apply / frost_saug_plan_words (the segmentation input pipeline, FROST_SAUG_*). */
 #ifndef FROST_DWQ_NC          /* (a -D override is a dev A/B build: the binding must be told the same value, FROST_DWQ_NC / FROST_COEF_ROWS_ALLOC / FROST_STATS_TABLES in the environment) */
 #define FROST_DWQ_NC 4
 #endif
@@ -921,6 +922,50 @@ int frost_caug_plan(const int32_t* sizes, int n, int size, double scale_lo, doub
 int frost_caug_eval_plan(const int32_t* sizes, int n, int size, int resize, int32_t* plan, void* stream);
 int frost_caug_apply(const uint8_t* images, const int32_t* sizes, const int32_t* plan, int n, int hmax, int wmax, int size, float mean0, float mean1, float mean2,
                      float std0, float std1, float std2, int channels_last, float* x, void* stream);
+
+/* ---- the segmentation input pipeline (Semantic_Segmentation/utilities/data_transforms.py: RandomFlip / RandomScale / RandomCrop / Normalize in the PASCAL VOC and the
+ * Cityscapes order for training, Resize -> Normalize or Normalize alone for validation) -----------------------------------------------------------------------------
+ * Two halves, as above.  A plan record says to which grid the WHOLE picture is resized, with which filter, and where the crop_w x crop_h output window lies in that
+ * grid; the window may leave the grid on every side, and what lies outside is padding (byte 0 of the picture, `ignore_idx` of the label map).  frost_saug_apply is a
+ * pure function of (images, labels, sizes, plan).  The definition all entries follow is frostnet_amd/seg_augment.py on CPU tensors: Pillow's antialiased two-pass
+ * resampler with the Lanczos or the triangle filter for the picture (fp64 weights, sin as a written-out fp64 sequence, 22-bit fixed-point coefficients with Pillow's
+ * rounding of negative weights, uint8 intermediate) and Pillow's nearest-neighbour index table, filled by repeated fp64 addition, for the label map.
+ * The plan record: FROST_SAUG_PLAN_WORDS int32 words per image, [n][FROST_SAUG_PLAN_WORDS]. */
+#define FROST_SAUG_PLAN_WORDS 8
+#define FROST_SAUG_FLAGS 0      /* FROST_SAUG_F_* bits */
+#define FROST_SAUG_RW 1         /* the grid the picture is resized to, 1 .. FROST_SAUG_MAX_GRID per side (without a filter bit: the image's own size) */
+#define FROST_SAUG_RH 2
+#define FROST_SAUG_OX 3         /* the output is the crop_w x crop_h window of the grid that starts here; negative = padding in front, |.| <= FROST_SAUG_MAX_GRID */
+#define FROST_SAUG_OY 4
+#define FROST_SAUG_PADW 5       /* RandomCrop's padding per side, for inspection (frost_saug_apply does not read them) */
+#define FROST_SAUG_PADH 6
+/* word 7: zero */
+#define FROST_SAUG_F_MIRROR 1          /* a left-right mirror ... */
+#define FROST_SAUG_F_FLIP_FIRST 2      /* ... of the source, in front of both resizes (PASCAL VOC order); clear: of the cropped window (Cityscapes order) */
+#define FROST_SAUG_F_LANCZOS 4         /* the picture's filter: Lanczos (a = 3), */
+#define FROST_SAUG_F_TRIANGLE 8        /* the triangle filter (wins when both are set), or neither: no resize, the grid is forced to the image's size */
+#define FROST_SAUG_MAX_GRID 8192       /* 2 * FROST_AUG_MAX_SIZE */
+#define FROST_SAUG_MAX_TAPS 13         /* the cap of frost_saug_apply's LDS path: taps per axis = 2 * ceil(support * max(image side / grid side, 1)) + 1 with support 3
+                                          (Lanczos) or 1 (triangle), i.e. Lanczos down to half size; beyond it the kernel's general path (same result) */
+/* frost_saug_plan: sizes [n][2] int32 (h, w); state: int64 {seed, images seen} in device memory.  Philox4x32-10 with frost_aug_plan's conventions and the counter word
+ * 0x53454741; every image uses one block: s = exp_poly(log_scale_lo + u (log_scale_hi - log_scale_lo)), RW = rint(w s) and RH = rint(h s) clamped into
+ * [1, FROST_SAUG_MAX_GRID], pad = max(0, (1 + crop - side) >> 1) per axis, OY = choice(RH + 2 pad_h - crop_h + 1) - pad_h, OX likewise, one coin for the mirror;
+ * flags = Lanczos | flip_first | mirror.  Writes plan, then a one-thread launch adds n to the images-seen word.  1 <= n <= 65535,
+ * -log 2 <= log_scale_lo <= log_scale_hi <= log 2 (with a rounding margin), 1 <= crop_w, crop_h <= FROST_AUG_MAX_SIZE.  Every sizes row is TRUSTED to be >= 1.
+ * frost_saug_eval_plan: crop_w, crop_h >= 1: the triangle filter to exactly that grid, window = the grid; crop_w = crop_h = 0: no filter, the grid is the image.
+ * frost_saug_apply: images [n][hmax][wmax][3] uint8 and labels [n][hmax][wmax] uint8, each pair in the top-left corner of its slot -> x fp32 [n][3][crop_h][crop_w], or
+ * [n][crop_h][crop_w][3] when channels_last, x[c] = ((v / 255) - mean_c) / std_c of the window's byte v, each operation rounded to fp32, and target
+ * [n][crop_h][crop_w], int64 when target_int64 and uint8 otherwise.  `tables`: n * (crop_w + crop_h) int32 words of workspace, the source column of every output
+ * column and the source row of every output row of the label map (-1: padding).  `parts`: 1 fills the tables, 2 writes x, 4 writes target (reads the tables); 7 is
+ * the whole call, anything else is for timing the launches apart.  Every sizes row is TRUSTED to lie in [1, hmax] x [1, wmax]; any plan contents are memory-safe
+ * (every word is clamped).  Nothing synchronises with the host. */
+int frost_saug_plan_words(void);
+int frost_saug_plan(const int32_t* sizes, int n, int crop_w, int crop_h, double log_scale_lo, double log_scale_hi, int flip_first, int64_t* state, int32_t* plan,
+                    void* stream);
+int frost_saug_eval_plan(const int32_t* sizes, int n, int crop_w, int crop_h, int32_t* plan, void* stream);
+int frost_saug_apply(const uint8_t* images, const uint8_t* labels, const int32_t* sizes, const int32_t* plan, int n, int hmax, int wmax, int crop_w, int crop_h,
+                     float mean0, float mean1, float mean2, float std0, float std1, float std2, int ignore_idx, int channels_last, int target_int64, int parts,
+                     int32_t* tables, float* x, void* target, void* stream);
 
 #ifdef __cplusplus
 }

@@ -157,6 +157,56 @@ def load_segmentation():
     return SegmentationLoss, MIOU, val_seg
 
 
+def load_seg_transforms():
+    """The reference's segmentation transforms (Semantic_Segmentation/utilities/data_transforms.py), imported in place.  torchvision is absent, so the three things the
+    file takes from it are restated with Pillow as torchvision defines them for PIL images: `Pad` (constant fill on (left/right, top/bottom), the palette of a mode-P
+    image kept), `functional.crop`, and `functional.to_tensor` / `normalize`; `Image.ANTIALIAS`, gone from Pillow 10, is today's `Image.LANCZOS`."""
+    if "ref_seg_transforms" in sys.modules:
+        return sys.modules["ref_seg_transforms"]
+    import numpy as np
+    from PIL import Image
+    if not hasattr(Image, "ANTIALIAS"):
+        Image.ANTIALIAS = Image.LANCZOS
+
+    class Pad:
+        def __init__(self, padding, fill=0, padding_mode="constant"):
+            assert padding_mode == "constant" and len(padding) == 2
+            self.padding, self.fill = padding, fill
+
+        def __call__(self, img):
+            pw, ph = self.padding
+            out = Image.new(img.mode, (img.size[0] + 2 * pw, img.size[1] + 2 * ph), self.fill)
+            if img.mode == "P" and img.getpalette() is not None:
+                out.putpalette(img.getpalette())
+            out.paste(img, (pw, ph))
+            return out
+
+    def crop(img, top, left, height, width):
+        return img.crop((left, top, left + width, top + height))
+
+    def to_tensor(img):
+        a = np.array(img, dtype=np.uint8)
+        return torch.from_numpy(a.reshape(a.shape[0], a.shape[1], -1)).permute(2, 0, 1).contiguous().to(torch.float32).div(255)
+
+    def normalize(t, mean, std):
+        m, s = torch.as_tensor(mean, dtype=t.dtype), torch.as_tensor(std, dtype=t.dtype)
+        return t.clone().sub_(m[:, None, None]).div_(s[:, None, None])
+
+    saved = {k: sys.modules.get(k) for k in ("torchvision", "torchvision.transforms", "torchvision.transforms.functional")}
+    tv, tvt, tvf = types.ModuleType("torchvision"), types.ModuleType("torchvision.transforms"), types.ModuleType("torchvision.transforms.functional")
+    tv.transforms, tvt.functional, tvt.Pad = tvt, tvf, Pad
+    tvf.crop, tvf.to_tensor, tvf.normalize = crop, to_tensor, normalize
+    sys.modules.update({"torchvision": tv, "torchvision.transforms": tvt, "torchvision.transforms.functional": tvf})
+    try:
+        return _load("ref_seg_transforms", f"{REF}/Semantic_Segmentation/utilities/data_transforms.py")
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
+
+
 def load_optimizer():
     if "ref_optimizer" in sys.modules:
         return sys.modules["ref_optimizer"]
