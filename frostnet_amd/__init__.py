@@ -5,7 +5,9 @@ from .augment import BaseTransform, SSDAugmentation, identity_plan, pad_images  
 from .cls_augment import ClassificationAugmentation, ClassificationEvalTransform  # noqa: F401
 from .seg import SegMeter, SegmentationLoss, seg_reference  # noqa: F401
 from .seg_augment import SegmentationAugmentation, SegmentationEvalTransform, pad_pairs  # noqa: F401
+from .seg_model import FrostNetSeg, LRASPPHead, frostnet_seg_base_1_0, frostnet_seg_large_1_0, frostnet_seg_small_1_0  # noqa: F401
 from .voc_eval import VOCEvaluator  # noqa: F401
 
 __all__ = ["load_library", "LIB_PATH", "SYMBOLS", "VOCEvaluator", "SegmentationLoss", "SegMeter", "seg_reference","SSDAugmentation", "BaseTransform", "identity_plan", "pad_images", "ClassificationAugmentation",
-           "ClassificationEvalTransform", "SegmentationAugmentation", "SegmentationEvalTransform", "pad_pairs"]
+           "ClassificationEvalTransform", "SegmentationAugmentation", "SegmentationEvalTransform", "pad_pairs", "FrostNetSeg", "LRASPPHead",
+           "frostnet_seg_large_1_0", "frostnet_seg_base_1_0", "frostnet_seg_small_1_0"]

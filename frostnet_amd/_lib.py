@@ -127,6 +127,18 @@ _PROTOS = {
     "frost_seg_workspace_bytes": [],
     "frost_seg_state_words": [I],
     "frost_seg_forward": [P, I, I, I, I, L, L, L, L, P, I, I, I, P, P, P, P, P, P],
+    "frost_seghead_pool": [P, I, I, I, I, I, I, I, I, P, P],
+    "frost_seghead_pool_f32": [P, I, I, I, I, I, I, I, I, P, P],
+    "frost_seghead_pool_bwd": [P, P, I, I, I, I, I, I, I, I, P, P],
+    "frost_seghead_pool_bwd_f32": [P, P, I, I, I, I, I, I, I, I, P, P],
+    "frost_seghead_gate_project": [P, P, P, P, I, I, I, I, I, I, I, P, P],
+    "frost_seghead_gate_project_f32": [P, P, P, P, I, I, I, I, I, I, I, P, P],
+    "frost_seghead_gate_project_bwd": [P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P, P],
+    "frost_seghead_gate_project_bwd_f32": [P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P, P],
+    "frost_seghead_logits": [P, P, P, P, I, I, I, I, I, I, I, P, P],
+    "frost_seghead_logits_f32": [P, P, P, P, I, I, I, I, I, I, I, P, P],
+    "frost_seghead_logits_bwd": [P, L, L, L, L, P, P, I, I, I, I, I, I, I, P, P, P, P, P],
+    "frost_seghead_logits_bwd_f32": [P, L, L, L, L, P, P, I, I, I, I, I, I, I, P, P, P, P, P],
     "frost_aug_plan_words": [],
     "frost_aug_plan": [P, P, P, I, I, P, P, P, P, P],
     "frost_aug_apply": [P, P, P, I, I, I, I, F, F, F, I, P, P],

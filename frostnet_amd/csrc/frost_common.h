@@ -124,6 +124,28 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// ---- bilinear upsampling, align_corners = True (frost_seg.hip, frost_seghead.hip; frostnet_amd/seg.py: _axis) ---------------------
+// host side: scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0
+// source index and weight of destination index d: s = scale * d, i0 = floor(s) held to in - 2 (so that i0 + 1 exists; the last pixel then has f = 1), f = s - i0
+__device__ __forceinline__ void seg_src(int d, float scale, int in, int& i0, float& f) {
+  const float s = scale * (float)d;
+  const int lim = in >= 2 ? in - 2 : 0;
+  int i = (int)s;
+  i = i < lim ? i : lim;
+  i0 = i; f = s - (float)i;
+}
+// the first d of [0, out] whose i0 is >= c (i0 is monotone in d)
+__device__ inline int seg_first(int c, float scale, int in, int out) {
+  if (c <= 0) return 0;
+  if (c > (in >= 2 ? in - 2 : 0)) return out;
+  int g = (int)ceilf((float)c / scale);          // in >= 3 here: scale > 0
+  g = g < 0 ? 0 : (g > out ? out : g);
+  int i; float f;
+  while (g > 0) { seg_src(g - 1, scale, in, i, f); if (i >= c) --g; else break; }
+  while (g < out) { seg_src(g, scale, in, i, f); if (i < c) ++g; else break; }
+  return g;
+}
+
 // observer EMA + qparams, shared by every finalize-type kernel (Appendix B of SURVEY.md).
 // cur_lo/cur_hi: min/max of the current tensor. Writes all qrecord fields. One thread.
 // the record fields the update reads, fetched ahead of the dependent chain that produces cur_lo / cur_hi (a finalize tail is a chain of global round trips:

@@ -29,25 +29,7 @@ struct SegGeom {
   int tbytes;                      // 8: int64 targets, 1: uint8
 };
 
-// source index and weight of destination index d: s = scale * d, i0 = floor(s) held to in - 2 (so that i0 + 1 exists; the last pixel then has f = 1), f = s - i0
-__device__ __forceinline__ void seg_src(int d, float scale, int in, int& i0, float& f) {
-  const float s = scale * (float)d;
-  const int lim = in >= 2 ? in - 2 : 0;
-  int i = (int)s;
-  i = i < lim ? i : lim;
-  i0 = i; f = s - (float)i;
-}
-// the first d of [0, out] whose i0 is >= c (i0 is monotone in d)
-__device__ inline int seg_first(int c, float scale, int in, int out) {
-  if (c <= 0) return 0;
-  if (c > (in >= 2 ? in - 2 : 0)) return out;
-  int g = (int)ceilf((float)c / scale);          // in >= 3 here: scale > 0
-  g = g < 0 ? 0 : (g > out ? out : g);
-  int i; float f;
-  while (g > 0) { seg_src(g - 1, scale, in, i, f); if (i >= c) --g; else break; }
-  while (g < out) { seg_src(g, scale, in, i, f); if (i < c) ++g; else break; }
-  return g;
-}
+// (the index and weight rule of the upsampling, seg_src / seg_first, is in frost_common.h: the segmentation head's kernels follow the same one)
 // a target as 0 .. 256: 256 stands for every int64 value outside 0 .. 255 (outside the contract, never an index)
 __device__ __forceinline__ int seg_target(const void* t, int tbytes, int64_t idx) {
   if (tbytes == 1) return (int)((const uint8_t*)t)[idx];

@@ -16,6 +16,7 @@ The module tree stays the owner of every Parameter and buffer; parameter gradien
 `p.grad`), the same contract as the fake-quant runner, so the multi-tensor GradBoost step and the data-parallel all-reduce work
 on it unchanged and `statassist_qat_switch` keeps the optimizer state attached.  No CPU / torch-eager fallback: a missing library raises.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -23,7 +24,7 @@ import torch
 
 from . import _lib as L
 from ._lib import call, ptr, stream
-from .topology import (FEATURE_TAPS, SSD_TAPS, FloatLayer, GradArena, act_code, bind_block, bind_detector, bind_trunk, conv_out_hw, model_signature,
+from .topology import (FEATURE_TAPS, SEG_TAPS, SSD_TAPS, FloatLayer, GradArena, act_code, bind_block, bind_detector, bind_trunk, conv_out_hw, model_signature,
                        plan_block, plan_tree, round_up)
 
 STATS, EMIT, BRED, BDC = 0, 1, 2, 3
@@ -128,8 +129,12 @@ class FloatRunner(GradArena):
         self.stem, self.blocks, self.last = bind_trunk(plan, self._add)
         self.stage_ends, self.fc, self.drop_rate = plan.stage_ends, plan.classifier, plan.drop_rate
         self.extras, self.heads = bind_detector(plan, self._add)
+        self._bind_more()
         self._finish()
         self._stem_tmp = torch.zeros(self.stem.cout * 64, dtype=torch.float32, device=self.device)
+
+    def _bind_more(self):
+        """Layers a subclass binds behind the trunk's and the detector's (FloatSegRunner: the segmentation head)."""
 
     def _set_precision(self, precision):
         precision = precision or os.environ.get("FROST_FLOAT_PRECISION", "bf16")
@@ -658,3 +663,195 @@ class FloatSSDRunner(FloatRunner):
             d = self._conv_bwd(pw1, ptr(d.buf), d.c, True)
             g = self._sum(srcg[i + 2], d)
         self._trunk_bwd(None, dict(zip((self.stage_ends[i] for i in SSD_TAPS), (srcg[0], srcg[1], g))))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------- segmentation network
+class _FloatSegFunction(torch.autograd.Function):
+    """image -> stride-8 logits of the float FrostNetSeg; backward runs head -> trunk by hand and writes the parameter gradients into the arena."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, runner):
+        ctx.runner = runner
+        return runner._seg_impl(x, record=True)
+
+    @staticmethod
+    def backward(ctx, dout):
+        run = ctx.runner
+        run._begin_backward()
+        dc1, dc4 = run._head_bwd(dout)
+        run._trunk_bwd(None, dict(zip((run.stage_ends[i] for i in SEG_TAPS), (dc1, dc4))))
+        return None, None, None
+
+
+class FloatSegRunner(FloatRunner):
+    """frostnet_amd.seg_model.FrostNetSeg in float mode on the float kernels: the trunk with taps at x2 (stride 8) and x5 (stride 32), then the Lite R-ASPP head.
+    b0 and b1's conv + BatchNorm are ordinary float layers (_conv / _conv_bwd: batch statistics, running statistics, backward); the pool, the gate, `project`,
+    `auxlayer` and both upsamplings are csrc/frost_seghead.hip.  project(up(z)) is computed as up(project(z)): nothing of 128 channels exists at c1's resolution.
+    The logits are fp32 NHWC memory returned as a channels-last NCHW view; frost_seg_forward reads them through strides and hands back its gradient in the same
+    layout, which frost_seghead_logits_bwd reads through strides again: no copy on the way to the criterion or back."""
+
+    def _set_precision(self, precision):
+        def table(prec):
+            FloatRunner._set_precision(self, prec)
+            sfx = "_f32" if self.fp32 else ""
+            for n in ("pool", "pool_bwd", "gate_project", "gate_project_bwd", "logits", "logits_bwd"):
+                self._fn["sh_" + n] = "frost_seghead_" + n + sfx
+            return self._fn
+        self._fn32 = table("fp32")          # the entries of the head's c4-resolution part (_c4_scope)
+        table(precision)
+
+    @contextlib.contextmanager
+    def _c4_scope(self):
+        """The head's c4-resolution part -- b0, the pool, b1, gate + project and their backward -- runs in fp32 storage in BOTH modes: at stride 32 it is a few
+        per cent of the head's own traffic, and in bf16 storage b0's ReLU mask taken from a rounded conv output and the bf16 weight packs would put 3e-2 on dc4 and
+        on the head's parameter gradients, the first gradients of the whole backward.  Inside the scope the runner's entry table, storage type and `_new` are the
+        fp32 mode's; c4 is widened on entry (_widen) and the tap gradient at x5 is rounded once to the storage type on exit."""
+        if self.fp32:
+            yield
+            return
+        saved = (self.precision, self.fp32, self._adt, self._fn)
+        self.precision, self.fp32, self._adt, self._fn = "fp32", True, torch.float32, self._fn32
+        try:
+            yield
+        finally:
+            self.precision, self.fp32, self._adt, self._fn = saved
+
+    def _widen(self, a):
+        """The activation in fp32 storage (itself in fp32 mode)."""
+        if a.buf.dtype == torch.float32:
+            return a
+        f = FAct(torch.empty(a.npix * a.c + 64, dtype=torch.float32, device=self.device), a.n, a.h, a.w, a.c)
+        f.buf[: a.npix * a.c].copy_(a.buf[: a.npix * a.c].view(torch.bfloat16))
+        return f
+
+    def _bind_more(self):
+        self._bind_head(self.model.head, "head.")
+
+    def _bind_head(self, head, prefix=""):
+        if not 2 <= head.nclass <= 255:
+            raise ValueError(f"FloatSegRunner: 2 <= nclass <= 255 (the criterion's range), got {head.nclass}")
+        self.head = head
+        with self._c4_scope():              # fp32 layer records: fp32 weight packs, the fp32 MFMA
+            self.b0 = self._add(prefix + "lr_aspp.b0", head.lr_aspp.b0, "pw")
+            self.b1 = self._add(prefix + "lr_aspp.b1.1", head.lr_aspp.b1[1], "pw")
+
+    @classmethod
+    def for_head(cls, head, precision=None):
+        """Bind a single LRASPPHead (teacher-forced head tests: `head_step`, `head_eval`)."""
+        L.load_library()
+        r = cls.__new__(cls)
+        r._set_precision(precision)
+        r.model, r.device = head, next(head.parameters()).device
+        r._bind_params(list(head.parameters()))
+        r.layers, r.stem, r.last, r.fc, r.blocks = [], None, None, None, []
+        r._bind_head(head)
+        r._finish()
+        return r
+
+    def head_step(self, c1, c4, gout):
+        """One teacher-forced train-mode forward + backward of the bound head: (out, dc1, dc4) as fp32 NCHW; p.grad is written."""
+        call("frost_float_weight_prep", ptr(self._table), len(self.layers), stream())
+        out = self._head_fwd(self.to_act(c1), self.to_act(c4), True, True).contiguous()
+        self._grads_written = False              # a test entry: p.grad is overwritten, not accumulated
+        self._begin_backward()
+        dc1, dc4 = self._head_bwd(gout)
+        self._end_backward()
+        return out, dc1.float().contiguous(), dc4.float().contiguous()
+
+    def head_eval(self, c1, c4):
+        """Eval-mode forward of the bound head (running statistics) -> out as fp32 NCHW."""
+        call("frost_float_weight_prep", ptr(self._table), len(self.layers), stream())
+        call("frost_float_bn_eval", ptr(self._table), len(self.layers), stream())
+        return self._head_fwd(self.to_act(c1), self.to_act(c4), False, False).contiguous()
+
+    def _pooled_hw(self, h, w):
+        from .seg_model import check_pool_fits
+        (kh, kw), (sh, sw) = self.head.pool_kernel, self.head.pool_stride
+        check_pool_fits(h, w, (kh, kw))
+        return (h - kh) // sh + 1, (w - kw) // sw + 1
+
+    def _check_input(self, x, training):
+        """Before anything is launched: the c4 map holds the pool window, and (torch's BatchNorm2d rule) b1's BatchNorm sees more than one value per channel."""
+        if x.dim() != 4 or not x.is_cuda:
+            raise ValueError("expected an (N,3,H,W) tensor on the model's device")
+        n, h, w = x.shape[0], x.shape[2], x.shape[3]
+        for l in self.layers:               # forward order; only the stride-2 layers change the map size (every one pads (k - 1) / 2)
+            if l.stride == 2:
+                h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        ph, pw = self._pooled_hw(h, w)
+        if training and n * ph * pw == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size torch.Size([{n}, {self.b1.cout}, {ph}, {pw}])")
+
+    def forward(self, x):
+        """Stride-8 logits [N, nclass, h/8, w/8], fp32, channels-last."""
+        if self.model.training and torch.is_grad_enabled():
+            return _FloatSegFunction.apply(self._params[0], x, self)
+        return self._seg_impl(x, record=False)
+
+    def _seg_impl(self, x, record):
+        training = self.model.training
+        self._check_input(x, training)
+        _, outs = self._trunk(x, training, record)
+        c1, c4 = (outs[self.stage_ends[i]] for i in SEG_TAPS)
+        return self._head_fwd(c1, c4, training, record)
+
+    def _head_fwd(self, c1, c4, training, record):
+        head = self.head
+        if training and not (self.b0.bn.training and self.b1.bn.training):
+            raise NotImplementedError("BatchNorm in eval mode inside a training forward of the FLOAT model: the float HIP backward implements the batch-statistics gradient only")
+        if c1.c != head.inter_channels or c4.c != head.in_channels or c1.n != c4.n:
+            raise ValueError(f"LRASPPHead: expected c1 with {head.inter_channels} and c4 with {head.in_channels} channels, got {c1.c} and {c4.c}")
+        ph, pw = self._pooled_hw(c4.h, c4.w)
+        if training and c4.n * ph * pw == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size torch.Size([{c4.n}, {self.b1.cout}, {ph}, {pw}])")
+        (kh, kw), (sh, sw) = head.pool_kernel, head.pool_stride
+        nclass, cf = head.nclass, self.b0.cout
+        with self._c4_scope():
+            c4 = self._widen(c4)
+            feat1 = self._conv(self.b0, c4, training, record)
+            pooled = self._new(c4.n, ph, pw, c4.c)
+            call(self._fn["sh_pool"], ptr(c4.buf), c4.n, c4.h, c4.w, c4.c, kh, kw, sh, sw, ptr(pooled.buf), stream())
+            g = self._conv(self.b1, pooled, training, record)
+            p = torch.empty(c4.npix * nclass, dtype=torch.float32, device=self.device)
+            call(self._fn["sh_gate_project"], ptr(feat1.buf), ptr(g.buf), ptr(head.project.weight), ptr(head.project.bias), c4.n, c4.h, c4.w, ph, pw, cf, nclass,
+                 ptr(p), stream())
+        out = torch.empty(c1.n, c1.h, c1.w, nclass, dtype=torch.float32, device=self.device)
+        call(self._fn["sh_logits"], ptr(p), ptr(c1.buf), ptr(head.auxlayer.weight), ptr(head.auxlayer.bias), c1.n, c1.h, c1.w, c4.h, c4.w, c1.c, nclass,
+             ptr(out), stream())
+        if record:
+            self._seg = (c1, c4, feat1, g)
+        return out.permute(0, 3, 1, 2)
+
+    def _head_bwd(self, dout):
+        """dout: gradient of the logits (NCHW-contiguous or channels-last, read through strides) -> (dc1, dc4) FActs, the tap gradients at x2 and x5; the
+        gradients of project / auxlayer go into their arena views, b0's and b1's through _conv_bwd.  Call between _begin_backward and _end_backward."""
+        c1, c4, feat1, g = self._seg
+        self._seg = None
+        head = self.head
+        (kh, kw), (sh, sw) = head.pool_kernel, head.pool_stride
+        nclass, cf = head.nclass, self.b0.cout
+        d = dout if dout.dtype == torch.float32 else dout.float()
+        if tuple(d.shape) != (c1.n, nclass, c1.h, c1.w):
+            raise ValueError(f"the logits' gradient is {tuple(d.shape)}, expected {(c1.n, nclass, c1.h, c1.w)}")
+        if not (d.is_contiguous() or d.is_contiguous(memory_format=torch.channels_last)):
+            d = d.contiguous()
+        sn, sc, s_h, s_w = d.stride()
+        gv = self._gv
+        dc1 = self._new(c1.n, c1.h, c1.w, c1.c)
+        dp = torch.empty(c4.npix * nclass, dtype=torch.float32, device=self.device)
+        call(self._fn["sh_logits_bwd"], ptr(d), sn, sc, s_h, s_w, ptr(c1.buf), ptr(head.auxlayer.weight), c1.n, c1.h, c1.w, c4.h, c4.w, c1.c, nclass,
+             ptr(dc1.buf), ptr(gv[id(head.auxlayer.weight)]), ptr(gv[id(head.auxlayer.bias)]), ptr(dp), stream())
+        with self._c4_scope():
+            dfeat1 = self._new(c4.n, c4.h, c4.w, cf)
+            dg = self._new(g.n, g.h, g.w, cf)
+            scratch = torch.empty(c4.npix * cf, dtype=torch.float32, device=self.device)
+            call(self._fn["sh_gate_project_bwd"], ptr(feat1.buf), ptr(g.buf), ptr(dp), ptr(head.project.weight), c4.n, c4.h, c4.w, g.h, g.w, cf, nclass,
+                 ptr(gv[id(head.project.weight)]), ptr(gv[id(head.project.bias)]), ptr(dfeat1.buf), ptr(dg.buf), ptr(scratch), stream())
+            d0 = self._conv_bwd(self.b0, ptr(dfeat1.buf), cf, True)
+            dpool = self._conv_bwd(self.b1, ptr(dg.buf), cf, True)
+            dc4 = self._new(c4.n, c4.h, c4.w, c4.c)
+            call(self._fn["sh_pool_bwd"], ptr(dpool.buf), ptr(d0.buf), c4.n, c4.h, c4.w, c4.c, kh, kw, sh, sw, ptr(dc4.buf), stream())
+        if dc4.buf.dtype != self._adt:          # the tap gradient at x5 in the storage type of the trunk
+            wide, dc4 = dc4, self._new(c4.n, c4.h, c4.w, c4.c)
+            self._store(dc4.buf[: c4.npix * c4.c], wide.buf[: c4.npix * c4.c])
+        return dc1, dc4

@@ -12,6 +12,7 @@ import torch
 STAGES = ("layer1", "layer2", "layer3", "layer4", "layer5")
 FEATURE_TAPS = (0, 1, 2, 4)      # stage ends the features backbone returns: [x1, x2, x3, x5], x4 is skipped (frostnet_features.py:350)
 SSD_TAPS = (1, 2, 4)             # stage ends that are SSD sources (strides 8 / 16 / 32)
+SEG_TAPS = (1, 4)                # stage ends the segmentation head reads: x2 (stride 8, c1) and x5 (stride 32, c4)
 
 
 def round_up(a, b):

@@ -46,7 +46,8 @@ extern "C" {
  *          New entries (additive): frost_aug_plan / frost_aug_apply / frost_aug_plan_words (SSD training-time augmentation, the FROST_AUG_* plan record).
  *          New entries (additive): frost_caug_plan / frost_caug_eval_plan / frost_caug_apply / frost_caug_plan_words (the classifier's input pipeline, FROST_CAUG_*).
  *          New entries (additive): frost_seg_forward / frost_seg_workspace_bytes / frost_seg_state_words (segmentation criterion and mean-IoU counts).
- *          New entries (additive): frost_saug_plan / frost_saug_eval_plan / frost_saug_apply / frost_saug_plan_words (the segmentation input pipeline, FROST_SAUG_*). */
+ *          New entries (additive): frost_saug_plan / frost_saug_eval_plan / frost_saug_apply / frost_saug_plan_words (the segmentation input pipeline, FROST_SAUG_*).
+ *          New entries (additive): frost_seghead_pool / _pool_bwd / _gate_project / _gate_project_bwd / _logits / _logits_bwd and their _f32 forms (the Lite R-ASPP head). */
 #ifndef FROST_DWQ_NC          /* (a -D override is a dev A/B build: the binding must be told the same value, FROST_DWQ_NC / FROST_COEF_ROWS_ALLOC / FROST_STATS_TABLES in the environment) */
 #define FROST_DWQ_NC 4
 #endif
@@ -827,6 +828,41 @@ int frost_seg_workspace_bytes(void);
 int frost_seg_state_words(int c);
 int frost_seg_forward(const float* logits, int n, int c, int h, int w, int64_t sn, int64_t sc, int64_t sh, int64_t sw, const void* target, int target_bytes,
                       int H, int W, const float* class_wts, float* loss, float* dx, int64_t* state, void* workspace, void* stream);
+
+/* ---- Lite R-ASPP segmentation head of the float path (Semantic_Segmentation/model/layers/LRASPP.py; the definition, operation by operation, is
+ * frostnet_amd/seg_model.py: LRASPPHead on CPU tensors) -------------------------------------------------------------------------------------------------------------
+ * Activations and their gradients are NHWC in the storage type of the float path: bf16 (uint16_t) or, for the *_f32 entries, fp32.  Weights, biases, their
+ * gradients, p, dp, the logits and their gradient are fp32.  up() is the bilinear upsampling with align_corners = True of frost_seg_forward, horizontally first.
+ * One or two launches on `stream` per entry, no allocation, nothing synchronises with the host.
+ *   frost_seghead_pool       y [n][ph][pw][c] = the mean over windows (kh, kw) at stride (sh, sw), no padding, ph = (h - kh) / sh + 1 (floor); kh <= h, kw <= w.
+ *   frost_seghead_pool_bwd   dx [n][h][w][c] = (sum of dy over the windows that hold the pixel) / (kh kw) + addend (addend NULL: + 0); every element written once.
+ *   frost_seghead_gate_project      p [n][h4][w4][nclass] = w_proj (feat1 * up(hsig(g) -> h4 x w4)) + b_proj, hsig(v) = relu6(v + 3) / 6; feat1 [n][h4][w4][cf],
+ *                                   g [n][ph][pw][cf], w_proj [nclass][cf], 1 <= cf <= 128, 1 <= nclass <= 255.
+ *   frost_seghead_gate_project_bwd  dp -> dw_proj, db_proj (ADDED to what the buffers hold, with fp32 atomics: order-dependent in the last bits), dfeat1 [n][h4][w4][cf],
+ *                                   dg [n][ph][pw][cf] (the adjoint of up() applied to dz * feat1, times hsig'(g); written once).  scratch: n h4 w4 cf floats.
+ *   frost_seghead_logits     out [n][h1][w1][nclass] = up(p -> h1 x w1) + w_aux c1 + b_aux; c1 [n][h1][w1][c1ch], 1 <= c1ch <= 128.
+ *   frost_seghead_logits_bwd dout [n][nclass][h1][w1] through the element strides sn, sc, sh, sw -> dc1 (storage type), dw_aux / db_aux (ADDED, atomics),
+ *                            dp [n][h4][w4][nclass] = the adjoint of up() in gather form (written once, no atomics). */
+int frost_seghead_pool(const uint16_t* x, int n, int h, int w, int c, int kh, int kw, int sh, int sw, uint16_t* y, void* stream);
+int frost_seghead_pool_f32(const float* x, int n, int h, int w, int c, int kh, int kw, int sh, int sw, float* y, void* stream);
+int frost_seghead_pool_bwd(const uint16_t* dy, const uint16_t* addend, int n, int h, int w, int c, int kh, int kw, int sh, int sw, uint16_t* dx, void* stream);
+int frost_seghead_pool_bwd_f32(const float* dy, const float* addend, int n, int h, int w, int c, int kh, int kw, int sh, int sw, float* dx, void* stream);
+int frost_seghead_gate_project(const uint16_t* feat1, const uint16_t* g, const float* w_proj, const float* b_proj, int n, int h4, int w4, int ph, int pw, int cf,
+                               int nclass, float* p, void* stream);
+int frost_seghead_gate_project_f32(const float* feat1, const float* g, const float* w_proj, const float* b_proj, int n, int h4, int w4, int ph, int pw, int cf,
+                                   int nclass, float* p, void* stream);
+int frost_seghead_gate_project_bwd(const uint16_t* feat1, const uint16_t* g, const float* dp, const float* w_proj, int n, int h4, int w4, int ph, int pw, int cf,
+                                   int nclass, float* dw_proj, float* db_proj, uint16_t* dfeat1, uint16_t* dg, float* scratch, void* stream);
+int frost_seghead_gate_project_bwd_f32(const float* feat1, const float* g, const float* dp, const float* w_proj, int n, int h4, int w4, int ph, int pw, int cf,
+                                       int nclass, float* dw_proj, float* db_proj, float* dfeat1, float* dg, float* scratch, void* stream);
+int frost_seghead_logits(const float* p, const uint16_t* c1, const float* w_aux, const float* b_aux, int n, int h1, int w1, int h4, int w4, int c1ch, int nclass,
+                         float* out, void* stream);
+int frost_seghead_logits_f32(const float* p, const float* c1, const float* w_aux, const float* b_aux, int n, int h1, int w1, int h4, int w4, int c1ch, int nclass,
+                             float* out, void* stream);
+int frost_seghead_logits_bwd(const float* dout, int64_t sn, int64_t sc, int64_t sh, int64_t sw, const uint16_t* c1, const float* w_aux, int n, int h1, int w1, int h4,
+                             int w4, int c1ch, int nclass, uint16_t* dc1, float* dw_aux, float* db_aux, float* dp, void* stream);
+int frost_seghead_logits_bwd_f32(const float* dout, int64_t sn, int64_t sc, int64_t sh, int64_t sw, const float* c1, const float* w_aux, int n, int h1, int w1, int h4,
+                                 int w4, int c1ch, int nclass, float* dc1, float* dw_aux, float* db_aux, float* dp, void* stream);
 
 /* ---- SSD training-time augmentation (Object_Detection/utils/augmentations.py:400-417 SSDAugmentation, data/__init__.py:30-43 BaseTransform) ------------------------
  * Two halves.  frost_aug_plan takes every random decision of the reference's pipeline, in its order, and writes one record per image plus the transformed targets;

@@ -11,7 +11,7 @@ per recipe:
       threads, wall clock, and whether the device output is bit-equal to it
   (e) SegmentationEvalTransform.__call__ likewise (VOC: Resize to the crop size; Cityscapes: Normalize alone)
   (f) the segmentation criterion the pipeline feeds (SegmentationLoss forward + backward on stride-8 logits at the crop size, the recipe's class count) in the same
-      process, and the pipeline's time relative to it.  The project has no segmentation network on the device yet, so a whole training step is not measured.
+      process, and the pipeline's time relative to it.  The share of a whole training iteration is measured by tools/bench_seg_train.py.
 
     python tools/bench_seg_augment.py [--reps 20] [--rounds 5] [--out profiles/seg_augment.txt]
 """
@@ -224,7 +224,7 @@ for name in args.recipes.split(","):
 
     res_l = rounds({"criterion": loss_step})
     say(f"(f) SegmentationLoss forward + backward, {c} classes, stride-8 logits -> {cw} x {ch}, same process   {fmt(res_l['criterion'])}; the pipeline (b) takes "
-        f"{res['graph'][0] / res_l['criterion'][0]:.2f} x the criterion's time (no segmentation network on the device yet: a whole step is not measured)")
+        f"{res['graph'][0] / res_l['criterion'][0]:.2f} x the criterion's time (the share of a whole training iteration: tools/bench_seg_train.py)")
     del host, dev, x, t, tables, plans, logits, target
     torch.cuda.empty_cache()
 if args.out:

@@ -157,6 +157,15 @@ def load_segmentation():
     return SegmentationLoss, MIOU, val_seg
 
 
+def load_seg_head():
+    """The reference's Lite R-ASPP head (Semantic_Segmentation/model/layers/LRASPP.py: `_Head` over `_LRASPP`), imported in place."""
+    seg = f"{REF}/Semantic_Segmentation"
+    if seg not in sys.path:
+        sys.path.insert(0, seg)
+    from model.layers.LRASPP import _Head
+    return _Head
+
+
 def load_seg_transforms():
     """The reference's segmentation transforms (Semantic_Segmentation/utilities/data_transforms.py), imported in place.  torchvision is absent, so the three things the
     file takes from it are restated with Pillow as torchvision defines them for PIL images: `Pad` (constant fill on (left/right, top/bottom), the palette of a mode-P
