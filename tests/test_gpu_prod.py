@@ -604,7 +604,12 @@ def test_weight_gradient_stream_does_not_change_the_step(engine):
     Measured on the commit before the scheduling experiments were removed (largest per-parameter relative difference): (a) two repeats of the stream-on step
     2.06e-5 (layer1.0.reduce_conv's dbeta, a sum that cancels to ~0); (b) stream-on against stream-off 7.97e-5 (the stem's dgamma; two stream-off repeats differ by
     7.93e-5 as well, and the other on / off pairing by 2.06e-5: run-to-run variation of the fused kernels' atomics, not of the stream).  Bound = 4 x the larger =
-    3.19e-4 (the margin covers atomic-order variation between devices)."""
+    3.19e-4 (the margin covers atomic-order variation between devices).
+
+    Known: the step has a second, rare outcome that this test meets as a failure with always the same figures -- 1.44e-2 on layer1.0.reduce_conv's dbeta (a sum
+    that cancels: |difference| 4.3e-4 beside a dgamma of norm 10.3), 2.06e-3 on the stem's dgamma, 3.66e-4 on its dbeta, every other gradient within the bound.
+    It shows between two stream-OFF steps as well, with bit-equal logits and buffers, and whether the engine's torch.empty buffers hold zeros or garbage: it
+    is in the backward of the stem and layer1.0, not in the side stream, and its cause is not found."""
     torch.set_num_threads(16)
     log_on, g_on, forked_on = _small64_train_step(True)
     log_off, g_off, forked_off = _small64_train_step(False)
