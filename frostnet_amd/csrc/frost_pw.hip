@@ -79,6 +79,7 @@ __device__ __forceinline__ float row_sum_f(float v) {
 }
 
 __device__ __forceinline__ uint32_t pack_bf2(float a, float b) { return cvt_pk_bf16(a, b); }
+__device__ __forceinline__ int pw_opaque(int v) { asm volatile("" : "+v"(v)); return v; }       // the same value, but not a loop invariant to the optimiser
 
 // Direct-to-LDS staging of one 128-pixel tile (gl mode).  A tile is 128*rowbytes CONTIGUOUS bytes of the pixel-major
 // tensor (always a multiple of 1 KiB), so its LDS image is a linear copy: every wave-level global_load_lds_dwordx4 moves one
@@ -162,8 +163,28 @@ __device__ __forceinline__ uint32_t pw_trunc_bf2(float lo, float hi) {   // exac
 // tile (s_cbranch / exec masking around every guarded block, SGPRs spilled to VGPR lanes) beside ~190-320 VALU -- the scalar unit is shared
 // by the CU's four SIMDs.  With the shape known the guards fold away.  SP & 16: the last channel tile is partial (cout = 24, 40: the channel
 // bound stays a run-time test, so does the row alignment).
+// SP >> 8 != 0 = the whole shape is in the instance (fused backward of the layers the forms above do not fit): bits 8..15 = cin / 8, bits 16..23 = cout / 8, the low
+// bits as above.  Every size derived from the two (channel tiles, row strides, tile bytes, K steps of both GEMMs, the weight-gradient tile count) is a constant; the
+// channel tiles keep the generic deal (wave wc of group cg owns tiles (cg * WC + wc) * MIE ...: same summation order, same random draws per thread), but the channel
+// group loop is unrolled and a guard stays a run-time (wave-uniform) test only for the tiles that some channel waves of that group own and others do not -- one tile of
+// 5 over 2 channel waves (72 channels), one of 9 over 4 (144: the second group is that tile alone, the three waves without it skip the group), two of 11 (168).
+#define PW_SHAPE(CIN, COUT, LOW) ((LOW) | (((CIN) / 8) << 8) | (((COUT) / 8) << 16))
+template <int SP, int MODE, int WP>
+__device__ __forceinline__ PwP pw_shaped(const PwP& q) {
+  PwP p = q;
+  if constexpr ((SP >> 8) != 0) {
+    constexpr int CIN = ((SP >> 8) & 255) * 8, COUT = ((SP >> 16) & 255) * 8, CPAD = (COUT + 15) & ~15, WC = 8 / WP, MIE = SP & 7;
+    p.rowbytes = CIN; p.kstr = CIN; p.kc_bytes = CIN; p.nchunks = 1; p.KS = (CIN + 63) / 64; p.cout = COUT; p.cpad = CPAD; p.gl = 1; p.tile_bytes = BP * CIN; p.nbuf = 2;
+    p.g_bytes = 256 * COUT; p.o_bytes = 256 * COUT; p.io = 3; p.io_bytes = 2 * 256 * COUT + 64; p.KSd = (COUT + 31) / 32; p.dx_bytes = 256 * CIN;
+    p.mi_eff = MIE; p.ngroups = (CPAD / 16 + WC * MIE - 1) / (WC * MIE); p.csplit = 1; p.tile0 = 0; p.cres = 0; p.cvt = 0;
+  }
+  return p;
+}
 template <int MODE, int WP, bool RES, bool FULLT, int FTW = 0, int SP = 0>
-__global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) void k_pw(const PwP p) {
+__global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) void k_pw(const PwP p_) {
+  constexpr bool SHP = (SP >> 8) != 0;             // the whole shape is compile-time
+  constexpr int CGU = SHP ? 2 : 1;                 // ... and its (at most two) channel groups are unrolled
+  const PwP p = pw_shaped<SP, MODE, WP>(p_);
   constexpr bool FUSE = FTW > 0;
   // XB: the fused backward's weight gradient takes its B operand from a bf16 copy of the x tile made once per tile (in the dx tile's LDS, weight gradient BEFORE the data
   // gradient).  Measured per shape: it wins where a wave owns <= 2 weight-gradient tiles (16 -> 96 @112: 655 -> 612 us, 24 -> 72 @56: 192 -> 179) and loses where it owns 6 - 11
@@ -207,7 +228,7 @@ __global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) 
   const int lane = tid & 63, j = lane & 15, g = lane >> 4;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wp = w / WC, wc = w % WC;
-  const int CT = SPC ? (8 / WP) * MIE : (p.cpad >> 4);
+  const int CT = (SPC && !SHP) ? (8 / WP) * MIE : (p.cpad >> 4);
   const int mi_eff = SPC ? MIE : p.mi_eff;
 
   if (MODE == M_STATS) {
@@ -261,8 +282,8 @@ __global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) 
   // lane-local accumulators that live across the persistent tile loop (single channel group only)
   // BRED with WP==2 already holds 64 accumulator registers: deferring would spill (measured 2x slower)
   // few-tile (7x7) layers: the channel groups are divided among `csplit` sets of workgroups so the launch still fills the chip
-  const int bsplit = (int)blockIdx.x / p.nbt, bslot = (int)blockIdx.x - bsplit * p.nbt;
-  const int cg_lo = SPC ? 0 : (bsplit * p.ngroups) / p.csplit, cg_hi = SPC ? 1 : ((bsplit + 1) * p.ngroups) / p.csplit;
+  const int bsplit = SHP ? 0 : (int)blockIdx.x / p.nbt, bslot = (int)blockIdx.x - bsplit * p.nbt;
+  const int cg_lo = SPC ? 0 : (bsplit * p.ngroups) / p.csplit, cg_hi = SHP ? p.ngroups : (SPC ? 1 : ((bsplit + 1) * p.ngroups) / p.csplit);
   const bool defer = (WP != 2) && (cg_hi - cg_lo == 1);      // WP == 2 holds 64 accumulator registers already: deferring would spill
   long long st1[MI]; double st2[MI]; int smn[MI], smx[MI];       // STATS: lane's channel = ct*16 + j
   float br1[MI][4], br2[MI][4];                                     // BRED: lane's channels = ct*16 + 4g + r
@@ -305,7 +326,11 @@ __global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) 
     }
   }
 
+  const int lane0 = lane, j0 = j, g0 = g;
   for (int64_t tile = p.tile0 + bslot; tile < p.ntiles; tile += p.nbt) {
+    // shape in the instance: every per-lane LDS / global address of the tile body is lane index x constant + constant.  Hoisted out of the tile loop they are ~60 live
+    // registers (scratch at four waves per SIMD); derived from an opaque copy of the lane index they stay inside the iteration, mostly as instruction offsets
+    const int lane = SHP ? pw_opaque(lane0) : lane0, j = SHP ? pw_opaque(j0) : j0, g = SHP ? pw_opaque(g0) : g0;
     const int64_t p0 = tile * BP;
     const bool full = FULLT;
     if (gl) {
@@ -320,15 +345,20 @@ __global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) 
       }
       full_prev = full;
     }
+#pragma unroll CGU
     for (int cg = cg_lo; cg < cg_hi; ++cg) {
       const int ct0 = (cg * WC + wc) * mi_eff;
       int mi_n = CT - ct0; mi_n = mi_n < 0 ? 0 : (mi_n > mi_eff ? mi_eff : mi_n);
-      if (SPC) mi_n = MIE;
+      if (SPC && !SHP) mi_n = MIE;
+      // shape in the instance: tiles every channel wave of this group owns (m < mi_lo) and tiles none owns (m >= mi_hi) are decided at compile time
+      int mi_lo = CT - (cg * WC + WC - 1) * mi_eff, mi_hi = CT - cg * WC * mi_eff;
+      mi_lo = mi_lo < 0 ? 0 : (mi_lo > mi_eff ? mi_eff : mi_lo); mi_hi = mi_hi > mi_eff ? mi_eff : mi_hi;
+      auto mok = [&](int m) __attribute__((always_inline)) { return SHP ? (m < mi_hi && (m < mi_lo || m < mi_n)) : m < mi_n; };
       v4i acci[MI][NT]; v4f accf[MI][NT];
 #pragma unroll
       for (int m = 0; m < MI; ++m) {
         v4i init = (v4i){0, 0, 0, 0};
-        if (!BF && m < mi_n) {
+        if (!BF && mok(m)) {
           if (MODE == M_STATS) { const int c = -zpx * wsump[(ct0 + m) * 16 + j]; init = (v4i){c, c, c, c}; }
           else { const int4 ws = *(const int4*)(wsump + (ct0 + m) * 16 + 4 * g); init = (v4i){-zpx * ws.x, -zpx * ws.y, -zpx * ws.z, -zpx * ws.w}; }
         }
@@ -362,13 +392,13 @@ __global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) 
           }
           __syncthreads();
         }
-        if (mi_n > 0) {
+        if (mok(0)) {
           const int ks_n = kcw_pad >> 6; const int ks0 = kc0 >> 6;
           // non-resident weights come from L2 (~400+ cycles): the fragments of K-step ks+1 are requested before the MFMAs of ks
           auto load_a = [&](int ks, v4i (&dst)[MI]) __attribute__((always_inline)) {
 #pragma unroll
             for (int m = 0; m < MI; ++m)
-              if (m < mi_n) dst[m] = *(const v4i*)((RES ? wl : p.wpack) + ((((int64_t)(ct0 + m) * p.KS + ks0 + ks) * 64 + lane) << 4));
+              if (mok(m)) dst[m] = *(const v4i*)((RES ? wl : p.wpack) + ((((int64_t)(ct0 + m) * p.KS + ks0 + ks) * 64 + lane) << 4));
           };
           v4i afr[MI], afn[MI];
           if (APF) load_a(0, afr);
@@ -383,7 +413,7 @@ __global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) 
             if (APF) { if (ks + 1 < ks_n) load_a(ks + 1, afn); } else load_a(ks, afr);
 #pragma unroll
             for (int m = 0; m < MI; ++m) {
-              if (m < mi_n) {
+              if (mok(m)) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                   if (BF) accf[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, afr[m]), __builtin_bit_cast(v8bf, bfr[t]), accf[m][t], 0, 0, 0);
@@ -420,7 +450,7 @@ __global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) 
           // cvt + fma (sum of squares, fp32 within the tile -> double across tiles), half a min3 and half a max3.
 #pragma unroll
           for (int m = 0; m < MI; ++m) {
-            if (m >= mi_n) continue;
+            if (!mok(m)) continue;
             int a1 = 0; float a2 = 0.0f; int mn = INT32_MAX, mx = INT32_MIN;
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -454,7 +484,7 @@ __global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) 
         }
 #pragma unroll
         for (int m = 0; m < MI; ++m) {
-          if (m >= mi_n) continue;
+          if (!mok(m)) continue;
           const int ch0 = (ct0 + m) * 16 + 4 * g;          // 4 consecutive channels of this lane
           const bool chok = SPF || ch0 < p.cout;
           if (MODE == M_DGRAD) {
@@ -650,7 +680,7 @@ __global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) 
 #pragma unroll
         for (int i = 0; i < FTW; ++i) {
           const int tt = w + 8 * i;
-          if (tt < ntw) {
+          if (SHP ? (8 * i < ntw && (8 * i + 8 <= ntw || tt < ntw)) : tt < ntw) {          // shape in the instance: run-time only for the last, shared-out round of tiles
             const int a = tt / nbw, b = tt - a * nbw;
             const uint8_t* a_src = dct + (g * 8 + (j >> 2)) * rbd + (j & 3) * 8 + a * 32;
             const uint8_t* b_src = xb + (g * 8 + (j >> 2)) * rbx + (j & 3) * 8 + b * 32;
@@ -701,7 +731,7 @@ __global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) 
 #pragma unroll
         for (int i = 0; i < FTW; ++i) {
           const int tt = w + 8 * i;
-          if (tt < ntw) {
+          if (SHP ? (8 * i < ntw && (8 * i + 8 <= ntw || tt < ntw)) : tt < ntw) {          // shape in the instance: run-time only for the last, shared-out round of tiles
             const int a = tt / nbw, b = tt - a * nbw;
             const uint8_t* a_src = dct + (g * 8 + (j >> 2)) * rbd + (j & 3) * 8 + a * 32;
             const uint8_t* b_src = xs + (g * 8 + (j >> 1)) * cin + (j & 1) * 8 + b * 16;
@@ -764,7 +794,7 @@ __global__ __launch_bounds__(512, (FTW > 0) ? PW_FUSE_MINW : PW_MINW(MODE, WP)) 
 #pragma unroll
     for (int i = 0; i < FTW; ++i) {
       const int tt = w + 8 * i;
-      if (tt < ntw) {
+      if (SHP ? (8 * i < ntw && (8 * i + 8 <= ntw || tt < ntw)) : tt < ntw) {
         const int a = tt / nbw, b = tt - a * nbw;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1032,8 +1062,16 @@ extern "C" int frost_pw_conv_bwd_fused(const int8_t* x, const float* qrec_x, con
   pf.dxo_off = f.dxo_off; pf.dx_bytes = 256 * cin; pf.wtl_off = f.wtl_off; pf.wtl_bytes = f.wtl_bytes; pf.xb_off = f.xb_off;
   hipStream_t s = as_stream(stream);
   int rc;
+  // layers whose whole shape is in an instance (k_pw's SP >> 8): the 56 x 56 and 28 x 28 expand / reduce layers of FrostNet-Large, at any pixel count
+  static const int spec_on = getenv("FROST_PW_SPEC") ? atoi(getenv("FROST_PW_SPEC")) : 1;
+  const int shp = spec_on ? cin * 1000 + cout : 0;
   const int sp = (f.ftw == 2 && nfull >= 2048) ? (f.wp == 8 ? pw_spec<8>(pf, true) : (f.wp == 4 ? pw_spec<4>(pf, true) : 0)) : 0;
-  if (sp == 2) rc = launch_pw3<M_BDC, 8, true, true, 2, 2>(pf, f.lds, 0, nfull, s);
+  if (shp == 24072 && f.wp == 4 && f.ftw == 2 && p.mi_eff == 3) rc = launch_pw3<M_BDC, 4, true, true, 2, PW_SHAPE(24, 72, 3 | 16)>(pf, f.lds, 0, nfull, s);
+  else if (shp == 24144 && f.wp == 2 && f.ftw == 6 && p.mi_eff == 2) rc = launch_pw3<M_BDC, 2, true, true, 6, PW_SHAPE(24, 144, 2)>(pf, f.lds, 0, nfull, s);
+  else if (shp == 56168 && f.wp == 2 && f.ftw == 6 && p.mi_eff == 2) rc = launch_pw3<M_BDC, 2, true, true, 6, PW_SHAPE(56, 168, 2 | 16)>(pf, f.lds, 0, nfull, s);
+  else if (shp == 144040 && f.wp == 8 && f.ftw == 6 && p.mi_eff == 3) rc = launch_pw3<M_BDC, 8, true, true, 6, PW_SHAPE(144, 40, 3 | 8 | 16)>(pf, f.lds, 0, nfull, s);
+  else if (shp == 168040 && f.wp == 8 && f.ftw == 6 && p.mi_eff == 3) rc = launch_pw3<M_BDC, 8, true, true, 6, PW_SHAPE(168, 40, 3 | 16)>(pf, f.lds, 0, nfull, s);
+  else if (sp == 2) rc = launch_pw3<M_BDC, 8, true, true, 2, 2>(pf, f.lds, 0, nfull, s);
   else if (sp == 9) rc = launch_pw3<M_BDC, 8, true, true, 2, 9>(pf, f.lds, 0, nfull, s);
   else if (sp == 1) rc = launch_pw3<M_BDC, 8, true, true, 2, 1>(pf, f.lds, 0, nfull, s);
   else if (sp == 18) rc = launch_pw3<M_BDC, 8, true, true, 2, 18>(pf, f.lds, 0, nfull, s);
